@@ -22,8 +22,17 @@ fit (Gram + Cholesky + L⁻¹ + α + diag(A⁻¹) → NLML, LOO-CRPS, LOO-LogS) 
   GPU and on the host.  ``fitc.C4.cpu_baseline``: dense FITC ref-mirror (n³-extrapolated)
   and the Woodbury numpy restatement.
 
-Inputs are synthetic (SURVEY.md §8d generator) and resident in HBM before the
-timed region.  Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Inputs are synthetic (SURVEY.md §8d generator, fixed seeds: the same arguments give the
+same inputs on every run) and resident in HBM before the timed region.
+
+A plain run measures the headline only: set up, warm up, time ``--steps`` units, print the
+JSON line (``value``, ``ms_per_step``, the last timed unit's objectives and scores).  Every
+other leg listed above (``fitc``, the rooflines and kernel accounting, gradients, block-LOO,
+the surfaces, ``cpu_baseline`` / ``parity`` / ``c1``) runs only with ``--full``, where the
+``--no-*`` switches still drop single legs.  ``--dump-outputs DIR`` writes what the last
+timed unit returned (objectives, μ*, σ²*, scores) as ``DIR/<name>.npy``.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -730,12 +739,36 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def dump_outputs(path, fit, pred):
+    """--dump-outputs: what the caller of one timed unit receives — fit's objectives and
+    predict's (μ*, σ²*, scores) — one float64 .npy each (the headline's largest is n* values,
+    far below any size cap, so nothing is sampled).  Scalars are stored in the order of
+    gpscore's OBJ_NAMES / SCORE_NAMES, listed in names.json beside them."""
+    from gpscore._lib import OBJ_NAMES, SCORE_NAMES
+    mu, var, sc = pred
+    os.makedirs(path, exist_ok=True)
+    arrays = {"objectives": [fit.objectives[k] for k in OBJ_NAMES], "pred_mu": mu, "pred_var": var,
+              "scores": [sc[k] for k in SCORE_NAMES]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float64))
+    with open(os.path.join(path, "names.json"), "w") as f:
+        json.dump({"objectives": list(OBJ_NAMES), "scores": list(SCORE_NAMES)}, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: kernel accounting and "
+                         "rooflines, phases, gradients, block-LOO, FITC C5 / C4, the surfaces, and "
+                         "at N = 1 the CPU baselines with parity and C1 (the --no-* switches drop "
+                         "single legs); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned — objectives (5), pred_mu and "
+                         "pred_var (n*), scores (6), float64 — as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-fitc", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-grad", action="store_true")
@@ -754,7 +787,7 @@ def main():
                          "sockets; the rank-count and C5-vs-N=1 checks run as at N>1 (not a "
                          "performance run: the ranks share one GPU)")
     ap.add_argument("--write-c5-fixture", metavar="PATH", default=None,
-                    help="N = 1 only: write the C5 unit's rank-independent outputs (fitc_outputs) "
+                    help="N = 1 with --full only: write the C5 unit's rank-independent outputs (fitc_outputs) "
                          "to PATH — the fixture tests/golden/c5_n1_outputs.json that N > 1 runs "
                          "are checked against")
     ap.add_argument("--dry", action="store_true",
@@ -823,9 +856,12 @@ def main():
     gp.set_data(X, y)
     gp.set_test(Xt, yt)
 
+    last = {}  # what the most recent unit returned to its caller (--dump-outputs)
+
     def unit():
-        gp.fit(theta=th, return_loo=False)
-        return gp.predict(with_scores=True)
+        last["fit"] = gp.fit(theta=th, return_loo=False)
+        last["pred"] = gp.predict(with_scores=True)
+        return last["pred"]
 
     log(f"{args.config}: warmup")
     for _ in range(args.warmup):
@@ -834,6 +870,48 @@ def main():
     # headline pass: production configuration (side-stream overlap on, no events)
     t_full = timed(ctl, ctx, unit, args.steps)
     ms_full = 1e3 * t_full / args.steps
+    fit_last, pred_last = last["fit"], last["pred"]  # the last timed step's results
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fit_last, pred_last)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    res = {
+        "metric": METRIC,
+        "value": world * args.steps / t_full,
+        "unit": f"fit+predict+score units/s ({args.config} full GP, whole job)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_full,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic (SURVEY.md §8d generator; random-init theta fixed)",
+        "config": {"workload": f"{args.config} full GP fit(NLML+LOO-CRPS+LOO-LogS)+predict+score",
+                   "n": c["n"], "d": c["d"], "n_test": c["nt"], "kernel": "ARD",
+                   "parallelism": (("replicas on ONE GPU, RCCL functional test (--one-gpu-rccl)"
+                                    if args.one_gpu_rccl else "replicas") if world > 1 else "single")},
+        "objectives": dict(fit_last.objectives), "scores": dict(pred_last[2]),
+    }
+    log("headline done: %.2f ms/step" % ms_full)
+    if args.full:
+        full_legs(args, ctl, ctx, gp, c, (X, y, Xt, yt), th, unit, ms_full, world, rank, local,
+                  res, failures)
+    if args.rehearse:
+        res["rehearsal"] = "all ranks on device 0, no RCCL: not a measurement"
+    if failures:
+        res["failures"] = failures
+    if rank == 0:
+        print(json.dumps(res))
+    if ctl.dist:
+        ctl.dist.destroy_process_group()
+    if failures:  # the line is printed (it carries the evidence), but the run fails
+        for f in failures:
+            print(f"[bench] FAILED: {f}", file=sys.stderr, flush=True)
+        sys.exit(4)
+
+
+def full_legs(args, ctl, ctx, gp, c, data, th, unit, ms_full, world, rank, local, res, failures):
+    """--full: every leg beyond the headline, added to the JSON line `res` (self-checks that
+    fail the run go to `failures`)."""
+    import gpscore
+    X, y, Xt, yt = data
     # kernel-accounting pass: same steps, one stream, hipEvents around every launch
     prof, ms_acct = kernel_pass(ctl, ctx, unit, args.steps)
     def upload():
@@ -855,18 +933,7 @@ def main():
             return None, None
     traffic, traffic_gram = read_traffic(args.traffic_json)
 
-    res = {
-        "metric": METRIC,
-        "value": world * args.steps / t_full,
-        "unit": f"fit+predict+score units/s ({args.config} full GP, whole job)",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_full,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic (SURVEY.md §8d generator; random-init theta fixed)",
-        "config": {"workload": f"{args.config} full GP fit(NLML+LOO-CRPS+LOO-LogS)+predict+score",
-                   "n": c["n"], "d": c["d"], "n_test": c["nt"], "kernel": "ARD",
-                   "parallelism": (("replicas on ONE GPU, RCCL functional test (--one-gpu-rccl)"
-                                    if args.one_gpu_rccl else "replicas") if world > 1 else "single")},
+    res.update({
         "roofline": roofline_mfma(prof, traffic, args.steps, alg_flop("full", c)),
         "roofline_gram": roofline_gram(prof, args.steps, traffic_gram),
         "roofline_trailing_update": roofline_trailing(prof, args.steps),
@@ -875,9 +942,9 @@ def main():
         "phases": unit_phases,
         "kernel_accounting": {"ms_per_step": ms_acct, "streams": 1,
                               "note": "second timed pass, overlap off, hipEvents around each launch"},
-    }
+    })
 
-    log("headline done: %.2f ms/step" % ms_full)
+    log("accounting and phases done")
     # ---------------- gradients (next-1: one GD iteration = fwd + analytic bwd) -------------
     if not args.no_grad:
         grad = {}
@@ -1054,18 +1121,6 @@ def main():
         if "fitc" in res and "C4" in res["fitc"]:
             log("FITC C4 CPU baseline")
             res["fitc"]["C4"]["cpu_baseline"] = fitc_cpu_baseline()
-    if args.rehearse:
-        res["rehearsal"] = "all ranks on device 0, no RCCL: not a measurement"
-    if failures:
-        res["failures"] = failures
-    if rank == 0:
-        print(json.dumps(res))
-    if ctl.dist:
-        ctl.dist.destroy_process_group()
-    if failures:  # the line is printed (it carries the evidence), but the run fails
-        for f in failures:
-            print(f"[bench] FAILED: {f}", file=sys.stderr, flush=True)
-        sys.exit(4)
 
 
 if __name__ == "__main__":

@@ -98,7 +98,7 @@ def test_fitc_blockloo_rccl_ranks(gpu_ctx, tmp_path, P, nfold, objective):
 def test_c5_full_size_rccl_two_ranks_bench_line(tmp_path):
     """BASELINE configs[4] (FITC n = 200 000, m = 4000, d = 16) at full size,
     rows sharded over 2 REAL RCCL ranks on the one GPU, through the bench's own N > 1 path
-    (`bench.py --gpus 2 --one-gpu-rccl`: the launcher, gps_comm_init, B's chunked ncclAllReduce
+    (`bench.py --full --gpus 2 --one-gpu-rccl`: the launcher, gps_comm_init, B's chunked ncclAllReduce
     beside the SYRK, the scalar all-reduces).  The line must carry RCCL's own rank counts agreeing
     on both ranks, the sharded C5 outputs equal to the committed N = 1 fixture
     (tests/golden/c5_n1_outputs.json) within its stated tolerance, the RCCL each rank ran, and
@@ -109,8 +109,8 @@ def test_c5_full_size_rccl_two_ranks_bench_line(tmp_path):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MASTER_ADDR"] = "127.0.0.1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--one-gpu-rccl",
-                        "--config", "C2", "--steps", "1", "--warmup", "1", "--no-grad", "--no-block",
-                        "--no-cpu"], env=env, capture_output=True, text=True, timeout=600,
+                        "--full", "--config", "C2", "--steps", "1", "--warmup", "1", "--no-grad",
+                        "--no-block", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600,
                        start_new_session=True)
     lines = [json.loads(s) for s in p.stdout.splitlines() if s.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stderr[-3000:])

@@ -68,8 +68,23 @@ def _sharded(P, X, y, Xt, yt, Z, th, with_grad, ar_chunks=None):
         finally:
             ctx.close()
 
+    return _join_ranks(rank_job, P)
+
+
+def _join_ranks(rank_job, P):
+    """Run rank_job(0..P-1) on P threads and return their results in rank order.  If ranks fail,
+    raise the error of the rank that failed on its own — the others only report that it left
+    the group — after printing every rank's message."""
     with ThreadPoolExecutor(max_workers=P) as ex:
-        return list(ex.map(rank_job, range(P)))
+        futs = [ex.submit(rank_job, r) for r in range(P)]
+        errs = [f.exception() for f in futs]
+    failed = [(r, e) for r, e in enumerate(errs) if e is not None]
+    if failed:
+        own = [e for _, e in failed if "left the group" not in str(e)]
+        for r, e in failed:
+            print(f"rank {r}: {type(e).__name__}: {e}")
+        raise (own or [failed[0][1]])[0]
+    return [f.result() for f in futs]
 
 
 def _whole(X, y, Xt, yt, Z, th, with_grad, gpu_ctx):

@@ -6,7 +6,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 NAME=${1:-base}
-B="bench.py --steps 5 --warmup 2 --no-grad --no-block --no-cpu"
+B="bench.py --full --steps 5 --warmup 2 --no-grad --no-block --no-cpu"
 for r in 1 2; do
   GPSCORE_LIB=$PWD/${LIBDIR:-tbin}/libgpscore_$NAME.so timeout -k 5 200 python -u $B > gpurun_out/ab_${NAME}_ref_$r.json 2>/dev/null || exit 1
   timeout -k 5 200 python -u $B > gpurun_out/ab_${NAME}_cur_$r.json 2>/dev/null || exit 1

@@ -8,6 +8,6 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES --kernel-trace \
   --output-format csv -d $OUT/pmc -o run \
-  -- python3 bench.py --steps 1 --warmup 1 --no-cpu --no-fitc --no-grad --no-block > $OUT/pmc.log 2>&1
+  -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-fitc --no-grad --no-block > $OUT/pmc.log 2>&1
 python3 tools/clock_summary.py $OUT > $OUT/summary.txt
 cat $OUT/summary.txt

@@ -15,7 +15,7 @@ for v in base var; do
 done
 timeout -k 5 200 /tmp/gb_base layout > gpurun_out/var_gb_base.txt 2>&1 || exit 1
 timeout -k 5 200 /tmp/gb_var layout > gpurun_out/var_gb_var.txt 2>&1 || exit 1
-B="bench.py --steps 5 --warmup 2 --no-fitc --no-grad --no-block --no-cpu"
+B="bench.py --full --steps 5 --warmup 2 --no-fitc --no-grad --no-block --no-cpu"
 for r in 1 2; do
   timeout -k 5 200 python -u $B > gpurun_out/var_bench_base_$r.json 2>/dev/null || exit 1
   GPSCORE_LIB=/tmp/var/libgpscore.so timeout -k 5 200 python -u $B > gpurun_out/var_bench_var_$r.json 2>/dev/null || exit 1

@@ -17,7 +17,7 @@ def kern(d, ind="  "):
         print("%s%-22s n=%6.1f  %9.3f ms  %s" % (ind, k, v["count"], v["ms"], extra))
 
 
-kern(r["kernels_per_step"])
+kern(r.get("kernels_per_step", {}))  # (only a --full line carries the per-kernel legs)
 for obj, g in r.get("grad", {}).items():
     if isinstance(g, dict):
         print("GRAD %-9s %.2f ms/iteration  %.1f TF" % (obj, g["ms_per_iteration"], g["tflops"]))

@@ -7,7 +7,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 REF=${REF:-r5}; T=${TAG:-tree_ab}
-B="--steps ${STEPS:-5} --warmup 2 --no-grad --no-block --no-cpu"
+B="--full --steps ${STEPS:-5} --warmup 2 --no-grad --no-block --no-cpu"
 for r in $(seq 1 ${ROUNDS:-3}); do
   (cd tbin/$REF && timeout -k 10 300 python -u bench.py $B > $GRAFT_REPO_ROOT/gpurun_out/${T}_ref_$r.json 2>/dev/null) || exit 1
   timeout -k 10 300 python -u bench.py $B > gpurun_out/${T}_cur_$r.json 2>/dev/null || exit 1
