@@ -54,8 +54,9 @@ enum {
 /* ABI version of this header; gps_version() returns the library's.  Bumped whenever an entry
  * point changes its arguments or an array it writes changes size (500: gps_ctx_stats takes a
  * capacity, gps_comm_info and gps_build_id added; 600: gps_phase_enable / gps_phase_collect /
- * gps_rccl_info added).  The binding refuses a mismatch at load. */
-#define GPS_ABI_VERSION 600
+ * gps_rccl_info added; 700: the joint test predictive, gps_*_predict_cov / _predict_joint /
+ * _predict_draws added).  The binding refuses a mismatch at load. */
+#define GPS_ABI_VERSION 700
 int gps_version(void);
 /* The SHA-256 (hex) of the sources the library was built from (csrc/, this header; computed by
  * gpscore/buildid.py at build time).  Writes at most cap-1 characters and a NUL; returns the
@@ -300,6 +301,45 @@ int gps_fitc_blockloo(gps_ctx* ctx, const double* theta, int n_ell, int nfold, i
  * row-major) at y with the draws given (ξ then ξ', num_sim × b each): the compat helper. */
 int gps_energy_score(gps_ctx* ctx, const double* m, const double* C, int64_t b, const double* y,
                      int num_sim, double beta, const double* draws, double* out);
+
+/* ---- joint test predictive -------------------------------------
+ * The FULL predictive covariance of the resident test rows, which gps_*_predict reduces to its
+ * diagonal: cal_mean_and_cov (KF:121-126) / spgp_cal_mean_and_cov (K20:76-83) as they return it,
+ * observation noise included:
+ *   full GP  Sigma = sigma²I + K** − K*f A⁻¹ Kf*          = sigma²I + K** − VᵀV,  V = L⁻¹Kf*
+ *   FITC     Sigma = sigma²I + K** − V₁ᵀV₁ + V₂ᵀV₂,  V₁ = Lm⁻¹Km*, V₂ = Lb⁻¹Km*
+ * and on it the paper's multivariate scores of held-out data — dss(mean_term, cov_term, num_va,
+ * va_y) (KF:556-563, dss KF:103-108) and ES(mean_term, cov_term, num_va, va_y) (KF:677-684, ES
+ * KF:70-101), which the scripts carry commented out — and joint draws mu + xi·L_Sigmaᵀ (as SD:174
+ * draws its data).  All need a fit and a test set resident, as gps_*_predict; a block is rows
+ * [r0, r1) with 0 <= r0 < r1 <= nt and at most 16384 rows (its V buffer at most 8 GiB).  They leave
+ * the fit, the test-side buffers of gps_*_predict and the FITC test pre-pass untouched: a
+ * gps_*_predict after them returns what it returned before, bitwise.  A context with a
+ * communicator is refused (-1): sharded joint scores are not implemented.  Sigma not positive
+ * definite: info > 0. */
+/* mu (b = r1 − r0, may be NULL) and cov (b×b, row-major, ldc >= b, BOTH triangles, bitwise
+ * symmetric) of rows [r0, r1) */
+int gps_full_predict_cov(gps_ctx* ctx, int64_t r0, int64_t r1, double* mu, double* cov,
+                         int64_t ldc);
+int gps_fitc_predict_cov(gps_ctx* ctx, int64_t r0, int64_t r1, double* mu, double* cov,
+                         int64_t ldc);
+enum { GPS_JOINT_DSS = 0, GPS_JOINT_ES = 1 };
+/* nblock contiguous blocks [⌊f·nt/k⌋, ⌊(f+1)·nt/k⌋) of the test rows (the KF:496-499 rule);
+ * value = Σ_f score(N(mu_f, Sigma_f), yt_f), block_values (nblock, may be NULL) the terms.
+ * GPS_JOINT_DSS: ½b·log2π + ½log|Sigma_f| + ½(yt_f − mu_f)ᵀSigma_f⁻¹(yt_f − mu_f) (KF:103-108).
+ * GPS_JOINT_ES: num_sim, beta and draws (2·num_sim·nt doubles) as gps_full_blockloo_es — block f
+ * holds ξ_f then ξ'_f, num_sim × b_f each; ignored for DSS (draws may be NULL).  nblock = 1 is the
+ * scripts' commented validation score.  Needs the test targets (set_test with yt). */
+int gps_full_predict_joint(gps_ctx* ctx, int nblock, int objective, int num_sim, double beta,
+                           const double* draws, double* value, double* block_values);
+int gps_fitc_predict_joint(gps_ctx* ctx, int nblock, int objective, int num_sim, double beta,
+                           const double* draws, double* value, double* block_values);
+/* out (nsamp × b, row-major) = mu + xi·L_Sigmaᵀ with xi (nsamp × b) the caller's N(0,1) draws and
+ * L_Sigma the lower Cholesky factor of the rows' covariance */
+int gps_full_predict_draws(gps_ctx* ctx, int64_t r0, int64_t r1, int nsamp, const double* xi,
+                           double* out);
+int gps_fitc_predict_draws(gps_ctx* ctx, int64_t r0, int64_t r1, int nsamp, const double* xi,
+                           double* out);
 
 /* ---- objective surfaces (contour-plot.R) ---------------
  * The objectives of CP.R:43-85 on a length-scale × noise grid, one small full GP per grid

@@ -1,7 +1,7 @@
 // C-ABI of libgpscore.so (declared in include/gpscore.h), core: context, device buffers,
 // options, profiling, the launch helpers and the recursive Cholesky + triangular-inverse driver,
 // and the L1 blocks.  The paths live in api_full.hip / api_fitc.hip / api_block.hip /
-// api_comm.hip (api_internal.h).  Host orchestration only; the arithmetic lives in kernels_*.hip.
+// api_joint.hip / api_comm.hip (api_internal.h).  Host orchestration only; the arithmetic lives in kernels_*.hip.
 //
 // Full GP, one fit (KF:239-245 LOO-CRPS, KF:329-334 NLML, KF:416-424 LOO-LogS):
 //   A = K(X,X) + σ²I (lower)  →  [L, L⁻¹] = potrf_inv(A)  →  β = L⁻¹y
@@ -682,7 +682,9 @@ std::vector<DBuf*> ctx_buffers(gps_ctx* ctx) {
                  &ctx->bEf, &ctx->bF, &ctx->ebuf, &ctx->edraws,
                  &ctx->bSg, &ctx->bBf, &ctx->bLf, &ctx->bldf, &ctx->bRem, &ctx->bW, &ctx->bkv,
                  &ctx->bLR, &ctx->bLRv,
-                 &ctx->ebuf_aux[0], &ctx->ebuf_aux[1], &ctx->ebuf_aux[2], &ctx->bPIs, &ctx->bRW, &ctx->escale, &ctx->bfv, &ctx->rpart, &ctx->dag_cnt, &ctx->sk_cnt, &ctx->dsig};
+                 &ctx->ebuf_aux[0], &ctx->ebuf_aux[1], &ctx->ebuf_aux[2], &ctx->bPIs, &ctx->bRW, &ctx->escale, &ctx->bfv, &ctx->rpart, &ctx->dag_cnt, &ctx->sk_cnt, &ctx->dsig,
+                 &ctx->jK, &ctx->jV, &ctx->jslab, &ctx->jS, &ctx->jL, &ctx->jLo, &ctx->jW, &ctx->jvec,
+                 &ctx->jE, &ctx->jdraws, &ctx->jxi, &ctx->jout};
 }
 
 

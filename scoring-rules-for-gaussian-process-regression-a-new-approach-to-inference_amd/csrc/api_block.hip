@@ -25,15 +25,6 @@ int64_t bounds_pad(const std::vector<int64_t>& bnd) {
   return pad_to(bmax);
 }
 
-struct EsArgs {
-  int S = 0;                      // draws per fold (num_sim: 300 at KF:652-655)
-  double beta = 1.0;              // the score's exponent (KF:70)
-  const double* draws = nullptr;  // device; fold f holds ξ_f then ξ'_f (S×b_f each, row-major)
-  double lam_lb = 0.0;            // λmin(C_f) >= lam_lb; <= 0: unknown, iterate to ‖T − I‖ ≈ 0
-  double diag_ub = 0.0;           // diag(C_f) <= diag_ub, so λmax <= b·diag_ub
-  double scale = 0.0;             // > 0: λmax(C_f) <= scale (‖C_f‖∞, full_blockloo), used instead
-};
-
 // Scaled Newton–Schulz schedule for a spectrum of C/s inside [x0, 1] (round 4).  The eigenvalue x
 // of Z_kY_k follows x ← f(x) = x(3 − x)²/4: ×2.25 per step while small (~20 steps from x0 = 8e-6).
 // Scaling the iterates by a scalar keeps the invariant Y_kZ_k⁻¹ = C/s (so the limit is still

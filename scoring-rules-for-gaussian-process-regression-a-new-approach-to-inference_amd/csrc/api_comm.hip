@@ -87,8 +87,12 @@ int allreduce_sum_impl(gps_ctx* ctx, double* buf, size_t count, hipStream_t s) {
     // (the previous sums of the other ranks read this rank's staging buffer: wait for them)
     for (int q = 0; q < G.n; ++q)
       if (q != r) HIPCHK(hipStreamWaitEvent(s, G.done[q], 0));
+    // (ready / done go through the rank's group stream: see LocalGroup::gstream)
+    hipStream_t gs = G.gstream[r];
     HIPCHK(hipMemcpyAsync(G.stage[r], buf, count * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipEventRecord(G.ready[r], s));
+    HIPCHK(hipEventRecord(G.staged[r], s));
+    HIPCHK(hipStreamWaitEvent(gs, G.staged[r], 0));
+    HIPCHK(hipEventRecord(G.ready[r], gs));
     if (int rc = group_barrier(ctx, G, count)) return rc;  // every rank's ready event recorded
     LocalSumPtrs sp;
     memset(&sp, 0, sizeof(sp));
@@ -97,7 +101,9 @@ int allreduce_sum_impl(gps_ctx* ctx, double* buf, size_t count, hipStream_t s) {
       if (q != r) HIPCHK(hipStreamWaitEvent(s, G.ready[q], 0));
     }
     HIPCHK(launch_local_sum(sp, G.n, (int64_t)count, buf, s));
-    HIPCHK(hipEventRecord(G.done[r], s));
+    HIPCHK(hipEventRecord(G.summed[r], s));
+    HIPCHK(hipStreamWaitEvent(gs, G.summed[r], 0));
+    HIPCHK(hipEventRecord(G.done[r], gs));
     return group_barrier(ctx, G, count);  // every rank's done event recorded before the next use
   }
   std::vector<double> mine(count);
@@ -199,10 +205,14 @@ int gps_comm_init_local(gps_ctx* ctx, int nranks, int rank, long long group) {
     G->stage_cap.assign(nranks, 0);
     G->ready.assign(nranks, nullptr);
     G->done.assign(nranks, nullptr);
+    G->staged.assign(nranks, nullptr);
+    G->summed.assign(nranks, nullptr);
+    G->gstream.assign(nranks, nullptr);
     if (G->device_ok)
       for (int q = 0; q < nranks; ++q) {
-        HIPCHK(hipEventCreateWithFlags(&G->ready[q], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&G->done[q], hipEventDisableTiming));
+        for (hipEvent_t* e : {&G->ready[q], &G->done[q], &G->staged[q], &G->summed[q]})
+          HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        HIPCHK(hipStreamCreateWithFlags(&G->gstream[q], hipStreamNonBlocking));
       }
     g_groups[group] = G;
   }

@@ -38,6 +38,7 @@ int gps_fitc_set_test(gps_ctx* ctx, const double* Xt, const double* yt, int64_t 
   if (!yt) zeros.assign(std::max<int64_t>(nt, 1), 0.0);
   if (int rc = upload(ctx, ctx->fyt, yt ? yt : zeros.data(), nt, 1, ctx->fnt_pad)) return rc;
   ctx->f_test = true;
+  ctx->f_have_yt = yt != nullptr;
   ctx->f_pre = ctx->f_pre_b = false;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;

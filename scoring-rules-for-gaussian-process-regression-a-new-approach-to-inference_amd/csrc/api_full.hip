@@ -38,6 +38,7 @@ int gps_full_set_test(gps_ctx* ctx, const double* Xt, const double* yt, int64_t 
   if (!yt) zeros.assign(nt, 0.0);
   if (int rc = upload(ctx, ctx->yt, yt ? yt : zeros.data(), nt, 1, ctx->nt_pad)) return rc;
   ctx->have_test = true;
+  ctx->have_yt = yt != nullptr;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
 }

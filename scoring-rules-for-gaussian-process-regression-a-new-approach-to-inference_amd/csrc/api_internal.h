@@ -3,7 +3,8 @@
 // translation units split by path (round 6): api.hip (context, options, profiling,
 // launch helpers, the recursive factorisation driver, L1 blocks), api_full.hip (full GP, CP.R
 // surfaces), api_fitc.hip (FITC fit / gradients / predict), api_block.hip (block-LOO and the
-// energy score), api_comm.hip (RCCL and the in-process communicator).
+// energy score), api_joint.hip (the joint test predictive: full covariance, DSS / ES test scores,
+// draws), api_comm.hip (RCCL and the in-process communicator).
 #pragma once
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -76,13 +77,25 @@ struct LocalGroup {
   std::vector<double*> stage;   // per rank, written only by its owner (grown after every reader)
   std::vector<size_t> stage_cap;
   std::vector<hipEvent_t> ready, done;  // per rank: partial staged / staging buffers read
+  // The events other ranks' threads wait on are recorded on a stream of the group's own per rank
+  // (gstream), never on a context's stream: a context's streams are captured into a hipGraph by
+  // its factorisations (potrf_inv), and a rank that reached its next all-reduce while another
+  // rank's thread was still capturing the stream that had last recorded such an event was refused
+  // by the runtime ("dependency created on uncaptured work in another stream").  staged / summed
+  // hand the rank's own stream over to its group stream (same thread, outside any capture).
+  std::vector<hipStream_t> gstream;
+  std::vector<hipEvent_t> staged, summed;
   ~LocalGroup() {
     for (hipEvent_t e : done)
       if (e) (void)hipEventSynchronize(e);
-    for (hipEvent_t e : ready)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : done)
-      if (e) (void)hipEventDestroy(e);
+    for (hipStream_t g : gstream)
+      if (g) {
+        (void)hipStreamSynchronize(g);
+        (void)hipStreamDestroy(g);
+      }
+    for (const std::vector<hipEvent_t>* v : {&ready, &done, &staged, &summed})
+      for (hipEvent_t e : *v)
+        if (e) (void)hipEventDestroy(e);
     for (double* p : stage)
       if (p) (void)hipFree(p);
   }
@@ -177,6 +190,7 @@ struct gps_ctx {
   int d = 0;
   double ytr_mean = 0, ytr_var = 1;
   bool have_data = false, have_test = false, fitted = false;
+  bool have_yt = false, f_have_yt = false;  // the resident test set came with targets (joint scores)
   Theta th;
   // ---- FITC state
   DBuf fX, fy, fXt, fyt, Z, Kmm, Am, Lm, Lb, ldm, ldb, Knm, q, lam, ilam, ys, slabB, red, c, tvec,
@@ -193,6 +207,10 @@ struct gps_ctx {
   DBuf escale;                  // ES: per fold ‖C_f‖∞, then the row-sum scratch
   DBuf bfv;                       // sharded FITC block-LOO: row counts, then the fold values
   DBuf rpart;                     // per-workgroup partials of the row finalisers (main stream)
+  // joint test predictive (api_joint.hip), the calls' own: the block's cross Gram, V, its split-K
+  // slabs when the stream's workspace is too small, Sigma_b, its L⁻¹ / L / factorisation workspace,
+  // vectors and scalars, the ES work area and draws, the padded ξ and the draws' product
+  DBuf jK, jV, jslab, jS, jL, jLo, jW, jvec, jE, jdraws, jxi, jout;
   int64_t fn = 0, fn_pad = 0, fnt = 0, fnt_pad = 0, m = 0, m_pad = 0, fn_total = 0, fnt_total = 0;
   int fd = 0;
   double f_ytr_mean = 0, f_ytr_var = 1;
@@ -217,6 +235,20 @@ struct gps_ctx {
 
 
 namespace gpsapi {
+
+// the energy score of one Gaussian (api_block.hip)
+struct EsArgs {
+  int S = 0;                      // draws per fold (num_sim: 300 at KF:652-655)
+  double beta = 1.0;              // the score's exponent (KF:70)
+  const double* draws = nullptr;  // device; fold f holds ξ_f then ξ'_f (S×b_f each, row-major)
+  double lam_lb = 0.0;            // λmin(C_f) >= lam_lb; <= 0: unknown, iterate to ‖T − I‖ ≈ 0
+  double diag_ub = 0.0;           // diag(C_f) <= diag_ub, so λmax <= b·diag_ub
+  double scale = 0.0;             // > 0: λmax(C_f) <= scale (‖C_f‖∞, full_blockloo), used instead
+};
+std::vector<int64_t> fold_bounds(int64_t n, int nfold);
+int es_fold(gps_ctx* ctx, hipStream_t s, DBuf& eb, bool conc, const EsArgs& es, const double* xi_src,
+            int64_t b, int64_t bp, const double* PI, const double* r, double trace_c, double* w,
+            double* G, int64_t ldg, double* g, double* out);
 
 extern thread_local std::string g_err;
 int fail(gps_ctx* ctx, int code, const std::string& msg);

@@ -443,6 +443,32 @@ hipError_t launch_es_dist(const double* Z, const double* Zh, int64_t ld, int S, 
 hipError_t launch_es_reduce(double* D, int64_t ldd, int S, int Sp, double beta, int grad,
                             double* rs, double* cs, double* out, hipStream_t s);
 
+// --- joint test predictive (kernels_joint.hip)
+// The covariance finisher: Sigma (bp×bp, ld bp, both triangles, diag(Sigma_b, I) on the padding) =
+// sf2·exp(−½‖(x_i − x_j)/ℓ‖²) + sn2·δ_ij − Σ_q slab_q[i][j] over the block's b rows x ([b][d]);
+// slab: ks slices of bp×bp, `stride` apart, lower 128-tiles valid, summed in slice order
+struct JointCovParams {
+  const double* x;
+  int b, bp, d;
+  double sf2, sn2;
+  double inv_ell[GPS_MAX_D];
+  const double* slab; int64_t stride; int ks;
+  double* out;
+};
+hipError_t launch_joint_cov(const JointCovParams& p, hipStream_t s);
+// r[i] = y[i] − mu[i] (i < b), 0 on the padding (i < bp)
+hipError_t launch_joint_resid(const double* y, const double* mu, int b, int bp, double* r,
+                              hipStream_t s);
+// *out = ½b·log2π + Σ_{i<b} logdiag[i] + ½Σ_{i<b} t[i]² (dss KF:103-108 with logdiag = log L_ii,
+// t = L⁻¹r)
+hipError_t launch_joint_dss(const double* logdiag, const double* t, int b, double* out,
+                            hipStream_t s);
+// dst[i] = +1 (i < npos), −1 (npos <= i < n): the per-k scale of the stacked FITC product
+hipError_t launch_sign_fill(double* dst, int npos, int n, hipStream_t s);
+// M[i][j] += mu[j] (i < rows, j < cols)
+hipError_t launch_row_add(double* M, int64_t ld, const double* mu, int rows, int cols,
+                          hipStream_t s);
+
 // --- FITC gradients (kernels_fitc_grad.hip)
 hipError_t launch_fitc_grad_terms(const double* y, const double* lam, const double* r,
                                   const double* g, int n, int n_pad, int obj, double n_total,

@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPSCORE_LIB", os.path.join(_HERE, "libgpscore.so"))
-ABI_VERSION = 600  # include/gpscore.h GPS_ABI_VERSION: the signatures below are this version's
+ABI_VERSION = 700  # include/gpscore.h GPS_ABI_VERSION: the signatures below are this version's
 GPS_N_STATS = 6
 GPS_COMM_NONE, GPS_COMM_RCCL, GPS_COMM_LOCAL = 0, 1, 2
 COMM_KINDS = {GPS_COMM_NONE: "none", GPS_COMM_RCCL: "rccl", GPS_COMM_LOCAL: "local"}
@@ -85,6 +85,12 @@ SIGNATURES = {
     "gps_energy_score": (_c_int, [_c_vp, _P, _P, _c_i64, _P, _c_int, _c_dbl, _P, _P]),
     "gps_fitc_predict": (_c_int, [_c_vp, _P, _P, _P]),
     "gps_fitc_intermediates": (_c_int, [_c_vp, _P, _P, _P, _P, _P]),
+    "gps_full_predict_cov": (_c_int, [_c_vp, _c_i64, _c_i64, _P, _P, _c_i64]),
+    "gps_fitc_predict_cov": (_c_int, [_c_vp, _c_i64, _c_i64, _P, _P, _c_i64]),
+    "gps_full_predict_joint": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_dbl, _P, _P, _P]),
+    "gps_fitc_predict_joint": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_dbl, _P, _P, _P]),
+    "gps_full_predict_draws": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _P, _P]),
+    "gps_fitc_predict_draws": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _P, _P]),
     "gps_full_surface": (_c_int, [_c_vp, _P, _P, _c_i64, _c_int, _c_dbl, _P, _c_i64, _P, _c_i64,
                                   _c_int, _P]),
     "gps_comm_unique_id": (_c_int, [_c_cp]),

@@ -124,13 +124,17 @@ def initial_theta(method, d, rng):
 
 
 def run_method(gp, data, method, rng, kind="full", m=20, itr=None, stale_noise=True,
-               num_sim=300):
+               num_sim=300, joint=()):
     """One fit (the method's SGD loop, GP.train) + test predictive + score bundle.
     Returns {mse, smse, logs, crps, msll, cover, theta, Z, failed}.  The predictive uses the
     final kernel parameters and, with stale_noise, the noise variance of the last iteration's
     forward pass: the scripts' module-global sigma_noise_sq is set before the last update and
     read by cal_mean_and_cov / spgp_cal_mean_and_cov.  The ES and KC fits turn
-    a non-PD factorisation into zero metrics (KF:726-732, K20:784-790); others raise."""
+    a non-PD factorisation into zero metrics (KF:726-732, K20:784-790); others raise.
+    ``joint``: names from ("dss", "es") — also report the multivariate score of the test targets
+    under the JOINT test predictive (GP.joint_score, one block: the calls the scripts carry
+    commented out at KF:556-563 and KF:677-684); off by default, so the series are unchanged."""
+    joint = tuple(joint)
     d = data["train_x"].shape[1]
     th0 = initial_theta(method, d, rng)
     itr = method.itr if itr is None else int(itr)
@@ -147,11 +151,12 @@ def run_method(gp, data, method, rng, kind="full", m=20, itr=None, stale_noise=T
             noise = float(series["theta"][itr - 2][-1]) if itr >= 2 else float(th0[2])
         gp.fit(theta=(theta[0], theta[1], noise), return_loo=False)
         _, _, sc = gp.predict(data["test_x"], data["test_y"], with_scores=True)
+        js = {k: gp.joint_score(k, num_sim=num_sim, rng=rng) for k in joint}
     except NotPositiveDefinite:
         if method.objective not in ("es", "kc"):
             raise
-        return dict({k: 0.0 for k in METRICS}, theta=None, Z=None, failed=True)
-    return {"mse": sc["test_mse"], "smse": sc["test_smse"], "logs": sc["test_logs"],
+        return dict({k: 0.0 for k in METRICS + joint}, theta=None, Z=None, failed=True)
+    return {**js, "mse": sc["test_mse"], "smse": sc["test_smse"], "logs": sc["test_logs"],
             "crps": sc["test_crps"], "msll": sc["test_msll"], "cover": sc["test_cover"],
             "theta": theta, "Z": series.get("Z"), "failed": False}
 
@@ -165,12 +170,13 @@ def run(sheets, TT=30, methods=None, kind="full", itr=None, seed=None, ctx=None,
     gp = GP(ctx=ctx)
     rng = np.random.default_rng(seed)
     rs = None if reseed else random.Random()
-    out = {name: {k: np.zeros(TT) for k in METRICS} for name in methods}
+    keys = METRICS + tuple(kw.get("joint", ()))
+    out = {name: {k: np.zeros(TT) for k in keys} for name in methods}
     n_pool = sheets["trainx"].shape[0]  # 10 000 in kin40k, the scripts' range(0, 10000)
     for j in range(TT):
         data = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
         for name, meth in methods.items():
             r = run_method(gp, data, meth, rng, kind=kind, itr=itr, **kw)
-            for k in METRICS:
+            for k in keys:
                 out[name][k][j] = r[k]
     return out

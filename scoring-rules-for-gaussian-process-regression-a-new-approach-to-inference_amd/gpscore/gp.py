@@ -23,6 +23,8 @@ from ._lib import (GPS_ARD, GPS_RBF, GPS_SURF_LOGS_ADD_NOISE, OBJ_NAMES, SCORE_N
                    SURFACE_NAMES, f64, ptr)
 
 BLOCK_OBJS = ["dss", "kc", "es"]  # GPS_BLOCK_DSS, GPS_BLOCK_KC, GPS_BLOCK_ES
+JOINT_OBJS = ["dss", "es"]        # GPS_JOINT_DSS, GPS_JOINT_ES
+JOINT_MAX_ROWS = 16384            # rows of one block of the joint test predictive
 
 
 def es_draws(n, nfold=4, num_sim=300, rng=None):
@@ -314,6 +316,84 @@ class GP:
         if with_scores:
             return mu, var, dict(zip(SCORE_NAMES, sc.tolist()))
         return mu, var
+
+    # ------------------------------------------------------- joint predictive
+    def _rows(self, rows):
+        """(r0, r1) of a row window of the resident test set (None: all of it), checked."""
+        if self._Xt is None:
+            raise ValueError("no test set: call set_test (or predict) first")
+        nt = self._nt
+        r0, r1 = (0, nt) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 < r1 <= nt:
+            raise ValueError(f"rows must satisfy 0 <= r0 < r1 <= nt = {nt}, got ({r0}, {r1})")
+        if r1 - r0 > JOINT_MAX_ROWS:
+            raise ValueError(f"a block holds at most {JOINT_MAX_ROWS} rows: use a row window")
+        return r0, r1
+
+    def _joint_name(self, what):
+        return ("gps_full_predict_" if self.kind == "full" else "gps_fitc_predict_") + what
+
+    def predict_cov(self, rows=None):
+        """Predictive mean and the FULL covariance (observation noise included, both triangles)
+        of the resident test rows — what cal_mean_and_cov (KF:121-126) / spgp_cal_mean_and_cov
+        (K20:76-83) return — formed on the device with the last fit's factor.  ``rows``: a
+        (r0, r1) window of the test set (default all; at most 16384 rows).  Returns (mu, cov)."""
+        r0, r1 = self._rows(rows)
+        self._ensure_resident()
+        b = r1 - r0
+        mu, cov = np.empty(b), np.empty((b, b))
+        self.ctx.call(self._joint_name("cov"), r0, r1, ptr(mu), ptr(cov), b)
+        return mu, cov
+
+    def joint_score(self, objective="dss", nblock=1, num_sim=300, beta=1.0, draws=None, rng=None,
+                    return_blocks=False):
+        """Multivariate score of the held-out targets under the joint test predictive, summed
+        over ``nblock`` contiguous blocks of the test rows (KF:496-499 bounds): "dss" — the
+        Dawid-Sebastiani score dss(mean_term, cov_term, num_va, va_y) (KF:103-108, the call the
+        scripts carry at KF:556-563); "es" — the energy score ES(mean_term, cov_term, num_va,
+        va_y) (KF:70-101, KF:677-684) from ``num_sim`` draws per block: pass ``draws``
+        (es_draws(nt, nblock, num_sim) layout) to fix them, else they come from ``rng``.
+        Needs a test set with targets.  Returns the value, or (value, per-block values)."""
+        if objective not in JOINT_OBJS:
+            raise ValueError(f"objective must be one of {JOINT_OBJS}")
+        if self._Xt is None:
+            raise ValueError("no test set: call set_test (or predict) first")
+        if self._yt is None:
+            raise ValueError("joint_score needs the test targets: set_test(Xt, yt)")
+        nt, nblock, num_sim = self._nt, int(nblock), int(num_sim)
+        if not 1 <= nblock <= min(64, nt):
+            raise ValueError("nblock must be in 1..min(64, nt)")
+        if objective == "es":
+            if draws is None:
+                draws = es_draws(nt, nblock, num_sim, rng)
+            draws = f64(draws).ravel()
+            if draws.size != 2 * num_sim * nt:
+                raise ValueError(f"draws must hold 2·num_sim·nt = {2 * num_sim * nt} values")
+        else:
+            draws = None
+        self._ensure_resident()
+        val, blocks = np.zeros(1), np.zeros(nblock)
+        self.ctx.call(self._joint_name("joint"), nblock, JOINT_OBJS.index(objective), num_sim,
+                      float(beta), ptr(draws), ptr(val), ptr(blocks))
+        return (float(val[0]), blocks) if return_blocks else float(val[0])
+
+    def sample(self, nsamp, rows=None, xi=None, rng=None):
+        """``nsamp`` joint draws of the observations at the resident test rows: mu + xi·Lᵀ with L
+        the Cholesky factor of predict_cov's covariance (as SD:174 draws its data).  ``xi``
+        (nsamp × b standard normals) fixes the draws; else they come from ``rng``."""
+        r0, r1 = self._rows(rows)
+        nsamp, b = int(nsamp), r1 - r0
+        if nsamp < 1:
+            raise ValueError("nsamp must be >= 1")
+        if xi is None:
+            xi = np.random.default_rng(rng).standard_normal((nsamp, b))
+        xi = f64(xi)
+        if xi.shape != (nsamp, b):
+            raise ValueError(f"xi must be nsamp × rows = {(nsamp, b)}, got {xi.shape}")
+        self._ensure_resident()
+        out = np.empty((nsamp, b))
+        self.ctx.call(self._joint_name("draws"), r0, r1, nsamp, ptr(xi), ptr(out))
+        return out
 
     # ----------------------------------------------------------------- score
     def score(self, mu, var, y_test, y_train):
