@@ -55,8 +55,9 @@ enum {
  * point changes its arguments or an array it writes changes size (500: gps_ctx_stats takes a
  * capacity, gps_comm_info and gps_build_id added; 600: gps_phase_enable / gps_phase_collect /
  * gps_rccl_info added; 700: the joint test predictive, gps_*_predict_cov / _predict_joint /
- * _predict_draws added).  The binding refuses a mismatch at load. */
-#define GPS_ABI_VERSION 700
+ * _predict_draws added; 800: the GEMM launch diagnostics gps_gemm_diag / gps_gemm_diag_check /
+ * gps_gemm_schedule added).  The binding refuses a mismatch at load. */
+#define GPS_ABI_VERSION 800
 int gps_version(void);
 /* The SHA-256 (hex) of the sources the library was built from (csrc/, this header; computed by
  * gpscore/buildid.py at build time).  Writes at most cap-1 characters and a NUL; returns the
@@ -164,6 +165,66 @@ int gps_ctx_stats(gps_ctx* ctx, int64_t* out, int cap);
  * bits rejected — kernels_potrf.hip).  Returns the queue length (writes at most cap words);
  * needs no device. */
 int gps_dag_task_list(int T, int flags, uint32_t* out, int cap);
+
+/* Diagnostics: ONE internal FP64 GEMM launch (csrc/kernels_gemm.hip's launch_gemm, through the
+ * same gemm() every production caller uses, on the context's main stream with that stream's
+ * split-K workspace and stream-K tickets) on host arrays copied to the device unpadded — the
+ * tests drive each kernel variant alone with it (tests/test_gpu_gemm_modes.py).  Not
+ * API: the description mirrors the internal GemmParams and changes with it.
+ *   lay_a / lay_b  0: A stored [i][k] / B stored [k][j]; 1: A stored [k][i] / B stored [j][k]
+ *   epi            0 store, 1 row squares, 2 column reduction, 3 row squares + row dot
+ *   tri            0 none, 1 k <= i, 2 k <= j, 3 k >= j, 4 k >= i (128-tile granular, shifted by
+ *                  tri_off), 5 per 16-column group [kr[2g], kr[2g+1])
+ *   tile           0 automatic (gemm_plan), 16 / 32 the small kernel (ksplit = waves per block:
+ *                  1, 2, 4), 64 / 128 the LDS kernel (ksplit = K slices)
+ *   use_ws         a split (ksplit > 1) goes through the workspace slabs and the reduction
+ *                  kernel; 0: slice s writes C + s·c_kslice_stride (beta 0, 128-tiles)
+ *   dep_mode       must be 0 (the dependent row-norm launch waits on a running factorisation)
+ * Array extents (doubles): A rows×lda with rows = M (lay_a 0) or K; B rows×ldb with rows = K
+ * (lay_b 0) or N; C M×ldc, or ksplit·c_kslice_stride for the unslabbed split (epi 0 only, else
+ * may be NULL); kscale K or NULL; w M (epi 2) or K (epi 3); kr 2·N/16 ints (tri 5); out0
+ * (N/128)×ld_out (epi 1, 3) or (M/128)×ld_out (epi 2); out1 as out0 (epi 2) or M (epi 3).  C,
+ * out0 and out1 go to the device as given and come back whole, so what a launch leaves unwritten
+ * keeps the caller's values. */
+typedef struct gps_gemm_desc {
+  int32_t lay_a, lay_b, epi;
+  int32_t M, N, K;               /* M, N multiples of 128, K of 16 */
+  int64_t lda, ldb, ldc;         /* even, at least the stored row length */
+  double alpha, beta;
+  int32_t tri, tri_off;          /* tri_off >= 0, a multiple of 16 */
+  int32_t lower_out, mirror;
+  int32_t kend;                  /* 0 or a multiple of 16: A's columns from kend on are zero */
+  int32_t tile, ksplit, map_mode;
+  int32_t use_ws, sk_alone, dep_mode;
+  int32_t reserved;
+  int64_t ld_out, c_kslice_stride;
+} gps_gemm_desc;
+/* the launch as launch_gemm chose it */
+enum { GPS_GEMM_PLAN_TILE = 0, GPS_GEMM_PLAN_KSPLIT = 1, GPS_GEMM_PLAN_MAP = 2,
+       GPS_GEMM_PLAN_SK_DP = 3, GPS_GEMM_PLAN_SK_WGS = 4, GPS_GEMM_PLAN_SLAB_XCD = 5,
+       GPS_GEMM_PLAN_GRID_X = 6, GPS_GEMM_PLAN_GRID_Y = 7, GPS_N_GEMM_PLAN = 8 };
+/* 0 if gps_gemm_diag would run the description, else -1 with the reason in
+ * gps_last_error(NULL): every description that could make a kernel read or write outside the
+ * arrays above, and every combination launch_gemm rejects, is refused here.  have_* say which
+ * optional arrays the caller has (kr itself is read: entries in [0, K], multiples of 16).
+ * Needs no device. */
+int gps_gemm_diag_check(const gps_gemm_desc* d, int have_c, int have_kscale, int have_w,
+                        const int32_t* kr, int have_out0, int have_out1);
+/* Runs the launch (after gps_gemm_diag_check, before anything touches the device: -1 on a
+ * refused description) and writes plan[GPS_N_GEMM_PLAN]. */
+int gps_gemm_diag(gps_ctx* ctx, const gps_gemm_desc* d, const double* A, const double* B,
+                  double* C, const double* kscale, const double* w, const int32_t* kr,
+                  double* out0, double* out1, int32_t* plan);
+/* Diagnostics, beside gps_dag_task_list: the work items the workgroups of that launch would run,
+ * enumerated on the host by the very functions the kernels call (csrc/gemm_schedule.h) — 8 ints
+ * per item: workgroup (x + y·grid_x), tile row ti, tile column tj (in units of the plan's tile),
+ * k begin, k end, K slice (small kernel: the wave's part), stream-K workspace slot (−1: none) and
+ * the ticket count the tile's last arriver waits for (0: no combine).  slots: the chip's workgroup
+ * slots for the stream-K tail (2 per CU; 0: no tail).  The option switches (GPS_OPT_STREAM_K, ...)
+ * apply as they are set.  Writes plan[GPS_N_GEMM_PLAN] and at most cap items; returns the item
+ * count, -1 on a refused description.  Needs no device. */
+int64_t gps_gemm_schedule(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int slots,
+                          int32_t* plan, int32_t* items, int64_t cap);
 
 /* on: 0 off, 1 per-kernel-class tags, 2 GEMM tags also carry layout/shape/tri/split-K/lda */
 int gps_prof_enable(gps_ctx* ctx, int on);

@@ -180,7 +180,8 @@ double gemm_flops(const GemmParams& p) {
   return 2.0 * M * N * K;
 }
 
-int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t st) {
+int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t st,
+         GemmLaunchInfo* info) {
   if (!st) st = ctx->stream;
   GemmParams q = p;
   if (q.map_mode == 0) q.map_mode = ctx->gemm_map;
@@ -207,7 +208,7 @@ int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t
     tag += buf;
   }
   Prof pr(ctx, tag, gemm_flops(p), 0, st);
-  HIPCHK(launch_gemm(al, bl, epi, q, st));
+  HIPCHK(launch_gemm(al, bl, epi, q, st, info));
   return 0;
 }
 

@@ -1,0 +1,245 @@
+// Diagnostics of the GEMM launcher (include/gpscore.h: gps_gemm_diag / gps_gemm_diag_check): one
+// internal launch on host arrays, so the tests can drive every kernel variant alone and compare
+// it exactly (tests/test_gpu_gemm_modes.py).  Nothing here is on a production path.
+#include "api_internal.h"
+
+// (the binding's ctypes structure is checked against the same size: tests/test_gemm_diag_args.py)
+static_assert(sizeof(gps_gemm_desc) == 128, "gps_gemm_desc layout");
+
+namespace gpsapi {
+
+// extents of the caller's arrays (doubles; kr in ints), 0 where the launch does not use one
+struct DiagExtents {
+  int64_t a, b, c, kscale, w, kr, out0, out1;
+};
+
+// The device-less validator: refuses (with a reason) every description whose launch could read
+// or write outside the arrays the caller hands over, every combination launch_gemm rejects, and
+// the dependent launch mode.  On success the arrays' extents.
+static bool diag_check(const gps_gemm_desc& d, bool have_c, bool have_kscale, bool have_w,
+                       const int32_t* kr, bool have_out0, bool have_out1, DiagExtents& x,
+                       std::string& why) {
+#define DIAG_REQ(cond, msg) \
+  do {                      \
+    if (!(cond)) {          \
+      why = msg;            \
+      return false;         \
+    }                       \
+  } while (0)
+  DIAG_REQ(d.dep_mode == 0, "dep_mode: the dependent row-norm launch cannot run alone");
+  DIAG_REQ((d.lay_a == LAY_N || d.lay_a == LAY_T) && (d.lay_b == LAY_N || d.lay_b == LAY_T),
+           "layouts must be 0 or 1");
+  DIAG_REQ(d.epi == EPI_STORE || d.epi == EPI_ROWSQ || d.epi == EPI_COLRED || d.epi == EPI_ROWSQ_DOT,
+           "unknown epilogue");
+  DIAG_REQ(d.M > 0 && d.N > 0 && d.K > 0 && d.M % GPS_TILE == 0 && d.N % GPS_TILE == 0 && d.K % 16 == 0,
+           "M and N must be positive multiples of 128, K of 16");
+  DIAG_REQ(d.M <= (1 << 18) && d.N <= (1 << 18) && (int64_t)d.M * d.N <= ((int64_t)1 << 27) &&
+               d.K <= 65536,
+           "M, N <= 2^18 with M*N <= 2^27, and K <= 65536");
+  DIAG_REQ(d.lda > 0 && d.lda % 2 == 0 && d.lda >= (d.lay_a == LAY_N ? d.K : d.M) && d.lda <= (1 << 20),
+           "lda must be even and at least A's stored row length");
+  DIAG_REQ(d.ldb > 0 && d.ldb % 2 == 0 && d.ldb >= (d.lay_b == LAY_N ? d.N : d.K) && d.ldb <= (1 << 20),
+           "ldb must be even and at least B's stored row length");
+  DIAG_REQ(d.tri >= TRI_NONE && d.tri <= TRI_KR_J, "unknown tri mode");
+  DIAG_REQ(d.tri_off >= 0 && d.tri_off % 16 == 0 && d.tri_off <= (1 << 24),
+           "tri_off must be a non-negative multiple of 16");
+  DIAG_REQ(d.tri_off == 0 || (d.tri >= TRI_K_LE_I && d.tri <= TRI_K_GE_I),
+           "tri_off needs one of the four triangular k-range modes");
+  if (d.tri == TRI_KR_J) {
+    DIAG_REQ(kr != nullptr, "TRI_KR_J needs kr");
+    for (int g = 0; g < 2 * (d.N / 16); ++g)
+      DIAG_REQ(kr[g] >= 0 && kr[g] <= d.K && kr[g] % 16 == 0,
+               "kr entries must be multiples of 16 in [0, K]");
+  }
+  DIAG_REQ(d.kend >= 0 && d.kend % 16 == 0, "kend must be 0 or a positive multiple of 16");
+  DIAG_REQ((d.lower_out == 0 || d.lower_out == 1) && (d.mirror == 0 || d.mirror == 1),
+           "lower_out and mirror are flags");
+  DIAG_REQ(!d.lower_out || d.M == d.N, "lower_out needs a square output");
+  DIAG_REQ(!d.mirror || d.lower_out, "mirror needs lower_out");
+  DIAG_REQ(d.tile == 0 || d.tile == 16 || d.tile == 32 || d.tile == 64 || d.tile == 128,
+           "tile must be 0, 16, 32, 64 or 128");
+  DIAG_REQ(d.ksplit >= 1 && d.ksplit <= 8, "ksplit must be in 1..8");
+  DIAG_REQ(d.map_mode >= 0 && d.map_mode <= 6, "map_mode must be in 0..6");
+  DIAG_REQ(d.map_mode != 3 || (!d.lower_out && d.tri >= TRI_K_LE_I && d.tri <= TRI_K_GE_I),
+           "map_mode 3 needs a triangular operand and a full output");
+  const bool small = d.tile == 16 || d.tile == 32;
+  if (small) {
+    DIAG_REQ(d.epi == EPI_STORE && !have_kscale, "the small kernel has no epilogue and no kscale");
+    DIAG_REQ(d.ksplit == 1 || d.ksplit == 2 || d.ksplit == 4,
+             "the small kernel runs 1, 2 or 4 waves per block");
+  }
+  DIAG_REQ(d.tile != 64 || d.epi == EPI_STORE, "the epilogues run on 128-tiles");
+  x = DiagExtents{};
+  x.a = (int64_t)(d.lay_a == LAY_N ? d.M : d.K) * d.lda;
+  x.b = (int64_t)(d.lay_b == LAY_N ? d.K : d.N) * d.ldb;
+  x.kscale = have_kscale ? d.K : 0;
+  x.kr = d.tri == TRI_KR_J ? 2 * (d.N / 16) : 0;
+  const bool split = !small && d.ksplit > 1;
+  if (d.epi == EPI_STORE) {
+    DIAG_REQ(have_c, "C is NULL");
+    DIAG_REQ(d.ldc > 0 && d.ldc % 2 == 0 && d.ldc >= d.N && d.ldc <= (1 << 20),
+             "ldc must be even and at least N");
+    x.c = (int64_t)d.M * d.ldc;
+    if (split && d.use_ws) {
+      DIAG_REQ((int64_t)d.ksplit * d.M * d.N <= kSplitWsDoubles, "the slabs exceed the workspace");
+    } else if (split) {
+      // (gemm() gives every 64-tile split the stream's slabs, so the unslabbed form is 128-tile)
+      DIAG_REQ(d.tile == 0 || d.tile == 128, "the unslabbed split runs on 128-tiles");
+      DIAG_REQ(d.beta == 0.0 && !d.mirror, "the unslabbed split needs beta 0 and no mirror");
+      DIAG_REQ(d.c_kslice_stride % 2 == 0 && d.c_kslice_stride >= x.c &&
+                   d.c_kslice_stride <= ((int64_t)1 << 32),
+               "c_kslice_stride must be even and at least M*ldc");
+      x.c = (int64_t)d.ksplit * d.c_kslice_stride;
+    }
+  } else {
+    DIAG_REQ(d.lay_a == LAY_N && d.lay_b == LAY_T, "the epilogues exist for A [i][k], B [j][k] only");
+    DIAG_REQ(d.tile == 0 || d.tile == 128, "the epilogues run on 128-tiles");
+    DIAG_REQ(d.ksplit == 1 && !d.mirror, "the epilogues take no split and no mirror");
+    DIAG_REQ(have_out0 && d.ld_out > 0 && d.ld_out <= (1 << 20), "out0 / ld_out missing");
+    if (d.epi == EPI_COLRED) {
+      DIAG_REQ(have_w && have_out1, "EPI_COLRED needs w and out1");
+      DIAG_REQ(d.ld_out >= d.N, "ld_out must be at least N");
+      x.w = d.M;
+      x.out0 = x.out1 = (int64_t)(d.M / GPS_TILE) * d.ld_out;
+    } else {
+      DIAG_REQ(d.ld_out >= d.M, "ld_out must be at least M");
+      x.out0 = (int64_t)(d.N / GPS_TILE) * d.ld_out;
+      if (d.epi == EPI_ROWSQ_DOT) {
+        DIAG_REQ(have_w && have_out1, "EPI_ROWSQ_DOT needs w and out1");
+        DIAG_REQ(d.tri == TRI_K_LE_J && d.K == d.tri_off + d.N,
+                 "EPI_ROWSQ_DOT needs TRI_K_LE_J with K = tri_off + N");
+        x.w = d.K;
+        x.out1 = d.M;
+      }
+    }
+  }
+#undef DIAG_REQ
+  return true;
+}
+
+// the description's scalar fields as GemmParams (the callers add the arrays)
+static GemmParams desc_params(const gps_gemm_desc& d) {
+  GemmParams p = gp0();
+  p.lda = d.lda; p.ldb = d.ldb; p.ldc = d.ldc; p.c_kslice_stride = d.c_kslice_stride;
+  p.M = d.M; p.N = d.N; p.K = d.K; p.alpha = d.alpha; p.beta = d.beta; p.ld_out = d.ld_out;
+  p.lower_out = d.lower_out; p.ksplit = d.ksplit; p.tri = d.tri; p.tri_off = d.tri_off;
+  p.map_mode = d.map_mode; p.tile = d.tile; p.mirror = d.mirror; p.kend = d.kend;
+  p.sk_alone = d.sk_alone;
+  return p;
+}
+// a slabbed 128-tile split names its slabs itself (gemm() hands the stream's workspace only to
+// unsplit launches and 64-tile splits)
+static bool own_slabs(const gps_gemm_desc& d) {
+  return d.ksplit > 1 && d.tile != 16 && d.tile != 32 && d.tile != 64 && d.use_ws;
+}
+
+}  // namespace gpsapi
+
+extern "C" {
+
+int gps_gemm_diag_check(const gps_gemm_desc* d, int have_c, int have_kscale, int have_w,
+                        const int32_t* kr, int have_out0, int have_out1) {
+  if (!d) return fail(nullptr, -1, "description is NULL");
+  DiagExtents x;
+  std::string why;
+  if (!diag_check(*d, have_c != 0, have_kscale != 0, have_w != 0, kr, have_out0 != 0,
+                  have_out1 != 0, x, why))
+    return fail(nullptr, -1, "gps_gemm_diag: " + why);
+  return 0;
+}
+
+int gps_gemm_diag(gps_ctx* ctx, const gps_gemm_desc* d, const double* A, const double* B,
+                  double* C, const double* kscale, const double* w, const int32_t* kr,
+                  double* out0, double* out1, int32_t* plan) {
+  // the description is judged first, without a device; only a runnable one reaches bind()
+  if (!d || !A || !B || !plan) return fail(ctx, -1, "gps_gemm_diag: NULL argument");
+  DiagExtents x;
+  std::string why;
+  if (!diag_check(*d, C != nullptr, kscale != nullptr, w != nullptr, kr, out0 != nullptr,
+                  out1 != nullptr, x, why))
+    return fail(ctx, -1, "gps_gemm_diag: " + why);
+  if (int rc = bind(ctx)) return rc;
+  hipStream_t s = ctx->stream;
+  auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };  // 16-byte aligned sub-buffers
+  HIPCHK(ensure(ctx, ctx->t0, (size_t)(even(x.a) + even(x.b)) * 8));
+  HIPCHK(ensure(ctx, ctx->t1, (size_t)std::max<int64_t>(even(x.c), 2) * 8));
+  HIPCHK(ensure(ctx, ctx->t2, (size_t)(even(x.kscale) + even(x.w) + even(x.out0) + even(x.out1) +
+                                       even((x.kr + 1) / 2) + 2) * 8));
+  double* dA = ctx->t0.d();
+  double* dB = dA + even(x.a);
+  double* dC = ctx->t1.d();
+  double* dks = ctx->t2.d();
+  double* dw = dks + even(x.kscale);
+  double* do0 = dw + even(x.w);
+  double* do1 = do0 + even(x.out0);
+  int* dkr = reinterpret_cast<int*>(do1 + even(x.out1));
+  auto up = [&](void* dst, const void* src, int64_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  HIPCHK(up(dA, A, x.a * 8));
+  HIPCHK(up(dB, B, x.b * 8));
+  HIPCHK(up(dC, C, x.c * 8));
+  HIPCHK(up(dks, kscale, x.kscale * 8));
+  HIPCHK(up(dw, w, x.w * 8));
+  HIPCHK(up(do0, out0, x.out0 * 8));
+  HIPCHK(up(do1, out1, x.out1 * 8));
+  HIPCHK(up(dkr, kr, x.kr * 4));
+  GemmParams p = desc_params(*d);
+  p.A = dA; p.B = dB; p.C = x.c ? dC : nullptr;
+  p.kscale = x.kscale ? dks : nullptr;
+  p.w = x.w ? dw : nullptr;
+  p.out0 = x.out0 ? do0 : nullptr; p.out1 = x.out1 ? do1 : nullptr;
+  p.kr = x.kr ? dkr : nullptr;
+  if (own_slabs(*d)) {
+    HIPCHK(ensure(ctx, ctx->ws_main, (size_t)kSplitWsDoubles * 8));
+    p.ws = ctx->ws_main.d();
+    p.ws_cap = kSplitWsDoubles;
+  }
+  GemmLaunchInfo info{};
+  if (int rc = gemm(ctx, d->lay_a, d->lay_b, d->epi, p, nullptr, &info)) return rc;
+  auto down = [&](void* dst, const void* src, int64_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+  };
+  HIPCHK(down(C, dC, x.c * 8));
+  HIPCHK(down(out0, do0, x.out0 * 8));
+  HIPCHK(down(out1, do1, x.out1 * 8));
+  HIPCHK(hipStreamSynchronize(s));
+  const int v[GPS_N_GEMM_PLAN] = {info.tile, info.ksplit, info.map_mode, info.sk_dp,
+                                  info.sk_wgs, info.slab_xcd, info.grid_x, info.grid_y};
+  for (int i = 0; i < GPS_N_GEMM_PLAN; ++i) plan[i] = v[i];
+  return 0;
+}
+
+int64_t gps_gemm_schedule(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int slots,
+                          int32_t* plan, int32_t* items, int64_t cap) {
+  if (!d || !plan || cap < 0 || (cap > 0 && !items) || slots < 0 || slots > 4096)
+    return fail(nullptr, -1, "gps_gemm_schedule: bad argument");
+  DiagExtents x;
+  std::string why;
+  if (!diag_check(*d, true, have_kscale != 0, true, kr, true, true, x, why))
+    return fail(nullptr, -1, "gps_gemm_schedule: " + why);
+  // the arrays are never touched (nothing is launched); what gemm() would hand the launch on the
+  // main stream is marked present: the stream's workspace and, with it, the stream-K tickets
+  static double mark[2];
+  GemmParams p = desc_params(*d);
+  p.A = p.B = mark; p.C = p.out0 = p.out1 = mark; p.w = mark;
+  p.kscale = have_kscale ? mark : nullptr;
+  p.kr = d->tri == TRI_KR_J ? kr : nullptr;
+  if (own_slabs(*d) || (d->epi == EPI_STORE && (p.ksplit == 1 || p.tile == 64))) {
+    p.ws = mark;
+    p.ws_cap = kSplitWsDoubles;
+    if (!own_slabs(*d) && slots > 0) {
+      p.sk_cnt = reinterpret_cast<int*>(mark);
+      p.sk_slots = slots;
+    }
+  }
+  GemmLaunchInfo info{};
+  const int64_t n = gemm_schedule(d->lay_a, d->lay_b, d->epi, p, info, items, cap);
+  if (n < 0) return fail(nullptr, -1, "gps_gemm_schedule: launch_gemm refuses the launch");
+  const int v[GPS_N_GEMM_PLAN] = {info.tile, info.ksplit, info.map_mode, info.sk_dp,
+                                  info.sk_wgs, info.slab_xcd, info.grid_x, info.grid_y};
+  for (int i = 0; i < GPS_N_GEMM_PLAN; ++i) plan[i] = v[i];
+  return n;
+}
+
+}  // extern "C"

@@ -308,7 +308,8 @@ hipEvent_t sync_event(gps_ctx* c);
 GemmParams gp0();
 const char* gemm_tag(int al, int bl, int epi, const GemmParams& p);
 double gemm_flops(const GemmParams& p);
-int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t st = nullptr);
+int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t st = nullptr,
+         GemmLaunchInfo* info = nullptr);
 int gram(gps_ctx* ctx, const char* tag, const double* x, int n, const double* xp, int m, int d,
          const Theta& th, double diag_add, int lower, int pad_identity, double* out, int64_t ldo,
          int M, int N, hipStream_t st = nullptr);

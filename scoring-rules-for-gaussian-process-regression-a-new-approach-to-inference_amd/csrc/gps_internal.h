@@ -108,6 +108,11 @@ constexpr int kSigInts = kSigQueue + 8 * 64;
 // launch shape chosen for a GEMM (tile edge, K slices); exposed for the microbenchmark
 struct GemmPlan { int tile, ksplit; };
 GemmPlan gemm_plan(int epi, const GemmParams& p, int64_t ws_cap_doubles);
+// what launch_gemm chose for one launch (diagnostics: gps_gemm_diag hands it to the tests, which
+// assert the variant they name is the one that ran): tile edge (16/32: the small kernel), K slices
+// (small kernel: waves per block), the tile order after the automatic choice, the stream-K tail's
+// data-parallel tiles and workgroups (0: no tail), the slice-major XCD deal, the kernel's grid
+struct GemmLaunchInfo { int tile, ksplit, map_mode, sk_dp, sk_wgs, slab_xcd, grid_x, grid_y; };
 extern int g_gram_reg;   // 1: d in {1, 8, 16} Gram builds use the register-resident kernel; 2 (the
                          //    default): d in {8, 16} builds of every shape (square lower ones such
                          //    as K_ff and K̃mm included) on the matrix-core kernel — equal to 1
@@ -262,7 +267,13 @@ struct SurfaceParams {
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 hipError_t launch_gram(const GramParams& p, hipStream_t s);
 // C = alpha * op(A) op(B) + beta * C with the epilogue selected by `epi`
-hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& p, hipStream_t s);
+// (info, if given, receives the launch's shape; it changes nothing of the launch)
+// (resolved, if given, receives the kernel's arguments instead of a launch: gemm_schedule)
+hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& p, hipStream_t s,
+                       GemmLaunchInfo* info = nullptr, GemmParams* resolved = nullptr);
+constexpr int kGemmItemInts = 8;
+int64_t gemm_schedule(int alay, int blay, int epi, const GemmParams& p, GemmLaunchInfo& info,
+                      int32_t* items, int64_t cap);
 
 // leaf of the recursive Cholesky: the diagonal 128×128 block, Cholesky + triangular inverse
 // in one workgroup (kernels_potrf.hip).  Reads the lower triangle of A (lda), writes L⁻¹

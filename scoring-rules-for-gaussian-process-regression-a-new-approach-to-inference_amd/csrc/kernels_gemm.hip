@@ -30,6 +30,7 @@
 // diagonal 128-blocks of a triangular factor are stored with explicit zeros
 // above the diagonal, so clipping at 64 or 128 granularity never drops a
 // nonzero) — no multiply touches a structurally zero tile.
+#include "gemm_schedule.h"
 #include "gps_internal.h"
 
 namespace gps {
@@ -40,90 +41,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // B staging registers in scratch (80 B/lane of spills in the k-major-B kernels)
 typedef double dv2 __attribute__((ext_vector_type(2)));
 
-constexpr int BK = 16;
-constexpr int GROUP_M = 8;
-
-// logical tile id -> (ti, tj).  Lower-triangular enumeration for SYRK outputs
-// (uniform work per tile); otherwise a grouped raster (GROUP_M tile rows at a
-// time, column-major inside the group) so the tiles resident together share A
-// and B panels in L2.
-//
-// Triangular operands (work per tile grows linearly along one tile index) are
-// issued heaviest-first and WITHOUT the XCD-contiguous remap.  Measured on
-// MI355X (tools/gemm_bench.cpp, 20096×5120×20096 TRMM): remap + any order
-// 35-45 TF/s, plain grouped order 64.6, heaviest-first 68.9.  Workgroups are
-// dealt to XCDs in block order, so an XCD whose slots are all held by long tiles
-// stalls the dispatch of every later block; equal-work neighbours in block order
-// (which land on different XCDs) avoid that.  Map 3 (the default for triangular
-// operands since the microbenchmark below) keeps that equal-work-per-XCD property
-// but gives each XCD a compact band of tiles: 70.7 TF/s on the same TRMM.
-__device__ __forceinline__ bool tile_of(const GemmParams& p, int t, int& ti, int& tj) {
-  if (p.lower_out) {
-    int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((r + 1) * (r + 2) / 2 <= t) ++r;
-    while (r * (r + 1) / 2 > t) --r;
-    ti = r;
-    tj = t - r * (r + 1) / 2;
-    return true;
-  }
-  if (p.map_mode == 3) {
-    // XCD-banded heaviest-first (triangular operands): block b runs on XCD b % 8;
-    // XCD x owns a contiguous band of the index that does NOT carry the triangular
-    // work and walks the other index heaviest-first, so every XCD gets the same work
-    // profile (balanced under in-order dispatch) while its ~64 resident tiles form a
-    // compact 2-D patch (both operand panels reused from its own L2).  Positions past
-    // the matrix edge are holes (the workgroup exits at once).
-    const int x = t & 7, i = t >> 3;
-    if (p.tri == TRI_K_LE_I || p.tri == TRI_K_GE_I) {  // work grows/shrinks with ti
-      const int bw = (p.tiles_n + 7) >> 3;
-      const int ri = i / bw;
-      tj = x * bw + i % bw;
-      ti = p.tri == TRI_K_LE_I ? p.tiles_m - 1 - ri : ri;
-      return tj < p.tiles_n && ri < p.tiles_m;
-    }
-    const int bh = (p.tiles_m + 7) >> 3;  // TRI_K_LE_J / TRI_K_GE_J: work follows tj
-    const int cj = i / bh;
-    ti = x * bh + i % bh;
-    tj = p.tri == TRI_K_LE_J ? p.tiles_n - 1 - cj : cj;
-    return ti < p.tiles_m && cj < p.tiles_n;
-  }
-  if (p.map_mode == 5) {
-    // XCD-banded 8×8 patches (the automatic order of the FITC row norms): as map 3, XCD x owns
-    // a band of the index that does not carry the triangular work, but its resident tiles form 8 (band) × 8
-    // (work index) patches, the work index walked heaviest-first patch by patch, so an 8×8
-    // group of tiles with neighbouring K ranges shares both operand panels in its L2.
-    const int x = t & 7, i = t >> 3;
-    const bool wi = p.tri == TRI_K_LE_I || p.tri == TRI_K_GE_I;  // work follows ti
-    const int nb = wi ? p.tiles_n : p.tiles_m, nw = wi ? p.tiles_m : p.tiles_n;
-    const int bb = (nb + 7) >> 3, per = ((bb + 7) >> 3) * 64;
-    const int wg = i / per, rem = i - wg * per, w = rem & 63;
-    const int bi = x * bb + (rem >> 6) * 8 + (w & 7), wk = wg * 8 + (w >> 3);
-    if (bi >= min(nb, x * bb + bb) || wk >= nw) return false;
-    const int widx = (p.tri == TRI_K_LE_I || p.tri == TRI_K_LE_J) ? nw - 1 - wk : wk;
-    ti = wi ? widx : bi;
-    tj = wi ? bi : widx;
-    return true;
-  }
-  const int per_group = GROUP_M * p.tiles_n;
-  const int g = t / per_group;
-  const int first = g * GROUP_M;
-  const int gm = min(GROUP_M, p.tiles_m - first);
-  const int tt = t - g * per_group;
-  ti = first + tt % gm;
-  tj = tt / gm;
-  if (p.map_mode != 0) return true;
-  if (p.tri == TRI_K_LE_I) ti = p.tiles_m - 1 - ti;       // K grows with ti
-  else if (p.tri == TRI_K_LE_J) tj = p.tiles_n - 1 - tj;  // K grows with tj
-  // TRI_K_GE_I / TRI_K_GE_J: K shrinks with the index, natural order is heaviest-first
-  return true;
-}
-
-// bijective XCD-contiguous remap: blocks b, b+8, b+16, ... (one XCD under the
-// observed round-robin dispatch) get consecutive logical tile ids.
-__device__ __forceinline__ int xcd_remap(int b, int nblk) {
-  const int q = nblk / 8, r = nblk % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
+// (the tile orders, K ranges and the stream-K partition — the kernels' integer schedule — are in
+// gemm_schedule.h, shared with the host diagnostic gemm_schedule below)
 
 // Row norms behind a running persistent factorisation (GemmParams::dep_mode).
 // Row tiles are dealt to the 8 XCDs in contiguous bands; the dependent launch's workgroup takes,
@@ -252,16 +171,11 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmParams p) {
   }
   if constexpr (EPI == EPI_ROWSQ || EPI == EPI_ROWSQ_DOT) {
     if (p.map_mode == 6) {
-      // paired column tiles (row norms over a triangular L⁻¹, work ∝ tj + 1): workgroup (ti, q)
-      // runs column tile T−1−q and then q, so every workgroup has the same K, (T + 1)·TILE — the
-      // grid is uniform like a square product's — in a grouped raster over XCD-contiguous ids
-      const int np = (p.tiles_n + 1) >> 1;
-      const int l = xcd_remap(blockIdx.x, gridDim.x);
-      const int per_group = GROUP_M * np, g = l / per_group, first = g * GROUP_M;
-      const int gm = min(GROUP_M, p.tiles_m - first), tt = l - g * per_group;
-      const int ri = first + tt % gm, q = tt / gm, qh = p.tiles_n - 1 - q;
+      // paired column tiles (pair_of): column tile T−1−q, then q
+      int ri, q, qh;
+      const bool second = pair_of(p, (int)blockIdx.x, (int)gridDim.x, ri, q, qh);
       gemm_tile<ALAY, BLAY, EPI, TILE>(p, ri, qh, 0, smem);
-      if (q < qh) {
+      if (second) {
         __syncthreads();  // (the first tile's reduction still reads the LDS the second stages into)
         gemm_tile<ALAY, BLAY, EPI, TILE>(p, ri, q, 0, smem);
       }
@@ -270,13 +184,11 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmParams p) {
   }
   int ti, tj;
   if (p.slab_xcd) {
-    // split-K, slice-major per XCD: the grid's (tile, slice) pairs in slice-major order, each XCD
-    // a contiguous run of them, so the workgroups resident on an XCD share one K slice's rows of
-    // both operands in its L2 (the tile-major remap spreads an XCD over every slice)
-    const int nt = (int)gridDim.x;
-    const int l = xcd_remap((int)(blockIdx.x + blockIdx.y * gridDim.x), nt * (int)gridDim.y);
-    if (!tile_of(p, l % nt, ti, tj)) return;
-    gemm_tile<ALAY, BLAY, EPI, TILE>(p, ti, tj, l / nt, smem);
+    // split-K, slice-major per XCD (slab_xcd_of)
+    int t, slice;
+    slab_xcd_of((int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y, t, slice);
+    if (!tile_of(p, t, ti, tj)) return;
+    gemm_tile<ALAY, BLAY, EPI, TILE>(p, ti, tj, slice, smem);
     return;
   }
   const int nblk = p.sk_wgs > 0 ? p.sk_dp : (int)gridDim.x;
@@ -324,24 +236,17 @@ __device__ void gemm_sk_block(const GemmParams& p, int s, double* smem) {
   constexpr int TILE = 128, MI = TILE / 32, TT = TILE * TILE;
   const int tiles = p.lower_out ? p.tiles_m * (p.tiles_m + 1) / 2 : p.tiles_m * p.tiles_n;
   const int nk = p.K / BK;
-  const int64_t I = (int64_t)(tiles - p.sk_dp) * nk, S = p.sk_wgs;
-  auto bnd = [&](int64_t q) { return q * I / S; };
-  auto owner = [&](int64_t x) {  // the block whose run holds iteration x
-    int64_t q = x * S / I;
-    while (q + 1 < S && bnd(q + 1) <= x) ++q;
-    while (q > 0 && bnd(q) > x) --q;
-    return (int)q;
-  };
+  const StreamKPart part{(int64_t)(tiles - p.sk_dp) * nk, (int64_t)p.sk_wgs};
   const int tid = threadIdx.x;
-  int64_t it = bnd(s);
-  const int64_t it1 = bnd(s + 1);
+  int64_t it = part.bnd(s);
+  const int64_t it1 = part.bnd(s + 1);
   while (it < it1) {
     const int u = (int)(it / nk);
     const int k0 = (int)(it - (int64_t)u * nk);
     const int k1 = (int)min<int64_t>(nk, k0 + (it1 - it));
     int ti, tj;
     tile_of(p, p.sk_dp + u, ti, tj);
-    const int s0 = owner((int64_t)u * nk), s1 = owner((int64_t)u * nk + nk - 1);
+    const int s0 = part.owner((int64_t)u * nk), s1 = part.owner((int64_t)u * nk + nk - 1);
     if (s0 == s1) {  // the whole tile in this run
       gemm_tile<ALAY, BLAY, EPI_STORE, TILE>(p, ti, tj, 0, smem);
       __syncthreads();  // (its last slice is still being read when the next run stages)
@@ -413,26 +318,15 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
   const int wr = wave >> 1, wc = wave & 1;
   const int row0 = ti * TILE, col0 = tj * TILE;
 
-  int kb = 0, ke = p.K;
-  switch (p.tri) {
-    case TRI_K_LE_I: ke = min(ke, p.tri_off + row0 + TILE); break;
-    case TRI_K_LE_J: ke = min(ke, p.tri_off + col0 + TILE); break;
-    case TRI_K_GE_J: kb = p.tri_off + col0; break;
-    case TRI_K_GE_I: kb = p.tri_off + row0; break;
-    case TRI_KR_J:
-      kb = p.kr[2 * (col0 / 16)];
-      ke = p.kr[2 * ((col0 + TILE) / 16 - 1) + 1];
-      break;
-    default: break;
-  }
+  int kb, ke;
+  tile_k_range(p, row0, col0, TILE, kb, ke);
   if (p.kend > 0 && ke > p.kend) ke = p.kend;  // (A's columns beyond kend are zero)
   if (kb_o >= 0) {  // a stream-K run: an explicit slice range of a uniform-K tile
     kb = kb_o;
     ke = ke_o;
   } else if (p.ksplit > 1) {
-    const int nk = ke > kb ? (ke - kb) / BK : 0;
-    const int s = kslice, q = nk / p.ksplit, r = nk % p.ksplit;
-    const int s0 = s * q + min(s, r), s1 = s0 + q + (s < r ? 1 : 0);
+    int s0, s1;
+    slice_part(ke > kb ? (ke - kb) / BK : 0, p.ksplit, kslice, s0, s1);
     ke = kb + s1 * BK;
     kb = kb + s0 * BK;
   }
@@ -657,40 +551,15 @@ __global__ __launch_bounds__(256) void gemm_f64_small_kernel(GemmParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int slot = wave / WPT, part = wave - slot * WPT;
   const int t = blockIdx.x * TPB + slot;
-  const int tm = p.M / TE, tn = p.N / TE;
   int ti = 0, tj = 0;
-  bool valid;
-  if (p.lower_out) {  // blocks (ti, tj) with tj/u <= ti/u, u = 64/TE, row-major over ti
-    constexpr int u = 64 / TE;
-    auto pre = [](int r) { const int a = r / u, b = r % u; return u * (u * a * (a + 1) / 2 + b * (a + 1)); };
-    valid = t < pre(tm);
-    if (valid) {
-      int lo = 0, hi = tm;
-      while (hi - lo > 1) { const int mid = (lo + hi) / 2; if (pre(mid) <= t) lo = mid; else hi = mid; }
-      ti = lo;
-      tj = t - pre(ti);
-    }
-  } else {
-    valid = t < tm * tn;
-    if (valid) { ti = t / tn; tj = t - ti * tn; }
-  }
+  const bool valid = small_block_of<TE>(p, t, ti, tj);
   if (WPT == 1 && !valid) return;  // (with WPT > 1 every wave reaches the LDS barrier)
   const int row0 = ti * TE, col0 = tj * TE;
-  int kb = 0, ke = p.K;
-  switch (p.tri) {
-    case TRI_K_LE_I: ke = min(ke, p.tri_off + row0 + TE); break;
-    case TRI_K_LE_J: ke = min(ke, p.tri_off + col0 + TE); break;
-    case TRI_K_GE_J: kb = p.tri_off + col0; break;
-    case TRI_K_GE_I: kb = p.tri_off + row0; break;
-    case TRI_KR_J:
-      kb = p.kr[2 * (col0 / 16)];
-      ke = p.kr[2 * ((col0 + TE) / 16 - 1) + 1];
-      break;
-    default: break;
-  }
+  int kb, ke;
+  tile_k_range(p, row0, col0, TE, kb, ke);
   const int nk = valid && ke > kb ? (ke - kb) / 16 : 0;
-  const int q = nk / WPT, rr = nk - q * WPT;
-  const int c0 = part * q + min(part, rr), c1 = c0 + q + (part < rr ? 1 : 0);
+  int c0, c1;
+  slice_part(nk, WPT, part, c0, c1);
   const int r = lane & 15, g = lane >> 4;
 
   typedef double Frag[G][R][4];
@@ -904,7 +773,8 @@ GemmPlan gemm_plan(int epi, const GemmParams& p, int64_t ws_cap) {
   return {64, ks};
 }
 
-hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipStream_t s) {
+hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipStream_t s,
+                       GemmLaunchInfo* info, GemmParams* resolved) {
   GemmParams p = pin;
   if (p.M % GPS_TILE || p.N % GPS_TILE || p.K % BK || p.M <= 0 || p.N <= 0)
     return hipErrorInvalidValue;
@@ -926,6 +796,11 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
     if (wpt != 1 && wpt != 2 && wpt != 4) return hipErrorInvalidValue;
     const int64_t tt = small_tiles(p, tile);
     const dim3 grid((unsigned)((tt * wpt + 3) / 4)), block(256);
+    if (info) *info = {tile, wpt, p.map_mode, 0, 0, 0, (int)grid.x, 1};
+    if (resolved) {  // (gemm_schedule: the kernel's arguments, nothing launched)
+      *resolved = p;
+      return hipSuccess;
+    }
     hipError_t err = hipErrorInvalidValue;
 #define GPS_SMALL_CASE(AL, BL, RR, W)                                                           \
     if (err == hipErrorInvalidValue && alay == AL && blay == BL && tile == 16 * RR && wpt == W) { \
@@ -981,6 +856,7 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
     q.prio = 0;
     q.slab_xcd = 0;
     q.sk_dp = q.sk_wgs = 0;
+    if (resolved) return hipErrorInvalidValue;  // (its tiles are taken at run time: no schedule)
     const dim3 grid((unsigned)(q.tiles_m * q.tiles_n)), block(256);
     hipLaunchKernelGGL((gemm_f64_kernel<LAY_N, LAY_T, EPI_ROWSQ, 128>), grid, block, 0, s, q);
     return hipGetLastError();
@@ -1020,8 +896,15 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
     if (tiles >= slots && rem > 0 && 4 * rem <= 3 * slots && rem <= kStreamKTiles &&
         (int64_t)(rem + slots) * 128 * 128 <= q.ws_cap && q.K / BK >= 2) {
       q.sk_dp = tiles - rem;
-      q.sk_wgs = slots;
-      tiles = q.sk_dp + slots;
+      // at most one workgroup per 16-deep slice of the tail, so that no run is empty: the
+      // combine takes a tile's partials from EVERY block owner(first slice) .. owner(last slice)
+      // and waits for that many tickets, which holds only if each of them ran part of the tile
+      // (with fewer slices than slots — 2944² at K = 32: 34 slices on 512 slots — blocks with
+      // empty runs lay between a tile's owners: the tile was never completed and its tickets
+      // stayed raised; tests/test_gpu_gemm_modes.py::test_stream_k_tail_exact)
+      const int64_t runs = (int64_t)rem * (q.K / BK);
+      q.sk_wgs = runs < slots ? (int)runs : slots;
+      tiles = q.sk_dp + q.sk_wgs;
     }
   }
   // raised MFMA-phase priority: 1 = the product / column-reduction launches only (C3 −1.3 %;
@@ -1032,6 +915,11 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
   q.slab_xcd = g_slab_xcd && q.ksplit > 1 && q.sk_wgs == 0 &&
                (q.map_mode == 0 || q.map_mode == 2) && (q.lower_out || q.tri == TRI_NONE);
   dim3 grid(tiles, q.ksplit), block(256);
+  if (info) *info = {tile, q.ksplit, q.map_mode, q.sk_dp, q.sk_wgs, q.slab_xcd, tiles, q.ksplit};
+  if (resolved) {
+    *resolved = q;
+    return hipSuccess;
+  }
   hipError_t err = hipErrorInvalidValue;
 #define GPS_GEMM_CASE(AL, BL, EP, T)                                                        \
   if (err == hipErrorInvalidValue && alay == AL && blay == BL && epi == EP && tile == T) { \
@@ -1062,6 +950,98 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s,
                      p.ws, p.ksplit, p.M, p.N, p.lower_out ? tile : 0, p.alpha, p.beta, p.C, p.ldc);
   return hipGetLastError();
+}
+
+// Diagnostics (gps_gemm_schedule): the work items a launch's workgroups would run, from the
+// kernels' own schedule functions (gemm_schedule.h) in the kernels' own dispatch order, without a
+// device.  kGemmItemInts ints per item: workgroup (x + y·grid_x), ti, tj, k begin, k end, K slice
+// (small kernel: the wave's part), stream-K workspace slot (−1: none) and the ticket count the
+// tile's last arriver waits for (0: the tile is whole in one run).  p.kr, if any, is a HOST array
+// here.  Returns the item count (writes at most cap items) or −1 for a launch launch_gemm refuses.
+int64_t gemm_schedule(int alay, int blay, int epi, const GemmParams& p, GemmLaunchInfo& info,
+                      int32_t* items, int64_t cap) {
+  GemmParams q;
+  if (launch_gemm(alay, blay, epi, p, nullptr, &info, &q) != hipSuccess) return -1;
+  int64_t n = 0;
+  auto emit = [&](int wg, int ti, int tj, int kb, int ke, int slice, int slot, int tickets) {
+    if (n < cap) {
+      int32_t* o = items + n * kGemmItemInts;
+      o[0] = wg; o[1] = ti; o[2] = tj; o[3] = kb; o[4] = ke > kb ? ke : kb; o[5] = slice; o[6] = slot;
+      o[7] = tickets;
+    }
+    ++n;
+  };
+  const int tile = info.tile;
+  if (tile == 16 || tile == 32) {  // gemm_f64_small_kernel
+    const int wpt = info.ksplit, tpb = 4 / wpt;
+    for (int b = 0; b < info.grid_x; ++b)
+      for (int wave = 0; wave < 4; ++wave) {
+        const int slot = wave / wpt, part = wave - slot * wpt;
+        int ti = 0, tj = 0;
+        const bool valid = tile == 16 ? small_block_of<16>(q, b * tpb + slot, ti, tj)
+                                      : small_block_of<32>(q, b * tpb + slot, ti, tj);
+        if (!valid) continue;
+        int kb, ke, c0, c1;
+        tile_k_range(q, ti * tile, tj * tile, tile, kb, ke);
+        slice_part(ke > kb ? (ke - kb) / 16 : 0, wpt, part, c0, c1);
+        emit(b, ti, tj, kb + 16 * c0, kb + 16 * c1, part, -1, 0);
+      }
+    return n;
+  }
+  auto tile_item = [&](int wg, int ti, int tj, int kslice) {  // gemm_tile's K range
+    int kb, ke;
+    tile_k_range(q, ti * tile, tj * tile, tile, kb, ke);
+    if (q.kend > 0 && ke > q.kend) ke = q.kend;
+    if (q.ksplit > 1) {
+      int s0, s1;
+      slice_part(ke > kb ? (ke - kb) / BK : 0, q.ksplit, kslice, s0, s1);
+      ke = kb + s1 * BK;
+      kb = kb + s0 * BK;
+    }
+    emit(wg, ti, tj, kb, ke, kslice, -1, 0);
+  };
+  const bool rowsq = epi == EPI_ROWSQ || epi == EPI_ROWSQ_DOT;
+  const bool remap = q.map_mode == 2 || (q.map_mode == 0 && q.tri == TRI_NONE);
+  for (int by = 0; by < info.grid_y; ++by)
+    for (int bx = 0; bx < info.grid_x; ++bx) {  // gemm_f64_kernel's dispatch
+      const int wg = bx + by * info.grid_x;
+      int ti, tj;
+      if (epi == EPI_STORE && tile == 128 && q.sk_wgs > 0 && bx >= q.sk_dp) {  // gemm_sk_block
+        const int s = bx - q.sk_dp;
+        const int tiles = q.lower_out ? q.tiles_m * (q.tiles_m + 1) / 2 : q.tiles_m * q.tiles_n;
+        const int nk = q.K / BK;
+        const StreamKPart part{(int64_t)(tiles - q.sk_dp) * nk, (int64_t)q.sk_wgs};
+        int64_t it = part.bnd(s);
+        const int64_t it1 = part.bnd(s + 1);
+        while (it < it1) {
+          const int u = (int)(it / nk);
+          const int k0 = (int)(it - (int64_t)u * nk);
+          const int k1 = (int)(nk < k0 + (it1 - it) ? nk : k0 + (it1 - it));
+          tile_of(q, q.sk_dp + u, ti, tj);
+          const int s0 = part.owner((int64_t)u * nk), s1 = part.owner((int64_t)u * nk + nk - 1);
+          if (s0 == s1) tile_item(wg, ti, tj, 0);
+          else emit(wg, ti, tj, k0 * BK, k1 * BK, 0, u + s, s1 - s0);
+          it += k1 - k0;
+        }
+        continue;
+      }
+      if (rowsq && q.map_mode == 6) {
+        int ri, c, ch;
+        const bool second = pair_of(q, bx, info.grid_x, ri, c, ch);
+        tile_item(wg, ri, ch, 0);
+        if (second) tile_item(wg, ri, c, 0);
+        continue;
+      }
+      if (q.slab_xcd) {
+        int t, slice;
+        slab_xcd_of(bx, by, info.grid_x, info.grid_y, t, slice);
+        if (tile_of(q, t, ti, tj)) tile_item(wg, ti, tj, slice);
+        continue;
+      }
+      const int nblk = q.sk_wgs > 0 ? q.sk_dp : info.grid_x;
+      if (tile_of(q, remap ? xcd_remap(bx, nblk) : bx, ti, tj)) tile_item(wg, ti, tj, by);
+    }
+  return n;
 }
 
 }  // namespace gps

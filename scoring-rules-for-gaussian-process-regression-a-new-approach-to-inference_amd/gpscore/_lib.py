@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPSCORE_LIB", os.path.join(_HERE, "libgpscore.so"))
-ABI_VERSION = 700  # include/gpscore.h GPS_ABI_VERSION: the signatures below are this version's
+ABI_VERSION = 800  # include/gpscore.h GPS_ABI_VERSION: the signatures below are this version's
 GPS_N_STATS = 6
 GPS_COMM_NONE, GPS_COMM_RCCL, GPS_COMM_LOCAL = 0, 1, 2
 COMM_KINDS = {GPS_COMM_NONE: "none", GPS_COMM_RCCL: "rccl", GPS_COMM_LOCAL: "local"}
@@ -42,6 +42,26 @@ _c_int, _c_i64, _c_dbl, _c_vp, _c_cp = (ctypes.c_int, ctypes.c_int64, ctypes.c_d
                                         ctypes.c_void_p, ctypes.c_char_p)
 _P = ctypes.POINTER(ctypes.c_double)
 
+_PI = ctypes.POINTER(ctypes.c_int32)
+
+
+class GemmDesc(ctypes.Structure):
+    """include/gpscore.h gps_gemm_desc: one internal GEMM launch (diagnostics, not API)."""
+    _fields_ = [("lay_a", ctypes.c_int32), ("lay_b", ctypes.c_int32), ("epi", ctypes.c_int32),
+                ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("lda", _c_i64), ("ldb", _c_i64), ("ldc", _c_i64),
+                ("alpha", _c_dbl), ("beta", _c_dbl),
+                ("tri", ctypes.c_int32), ("tri_off", ctypes.c_int32),
+                ("lower_out", ctypes.c_int32), ("mirror", ctypes.c_int32),
+                ("kend", ctypes.c_int32),
+                ("tile", ctypes.c_int32), ("ksplit", ctypes.c_int32), ("map_mode", ctypes.c_int32),
+                ("use_ws", ctypes.c_int32), ("sk_alone", ctypes.c_int32),
+                ("dep_mode", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ld_out", _c_i64), ("c_kslice_stride", _c_i64)]
+
+
+GEMM_PLAN_NAMES = ("tile", "ksplit", "map_mode", "sk_dp", "sk_wgs", "slab_xcd", "grid_x", "grid_y")
+
 # name -> (restype, argtypes); every symbol include/gpscore.h declares
 SIGNATURES = {
     "gps_version": (_c_int, []),
@@ -55,6 +75,11 @@ SIGNATURES = {
     "gps_ctx_set_option": (_c_int, [_c_vp, _c_int, _c_int]),
     "gps_ctx_stats": (_c_int, [_c_vp, _c_vp, _c_int]),
     "gps_dag_task_list": (_c_int, [_c_int, _c_int, _c_vp, _c_int]),
+    "gps_gemm_diag_check": (_c_int, [ctypes.POINTER(GemmDesc), _c_int, _c_int, _c_int, _PI, _c_int,
+                                     _c_int]),
+    "gps_gemm_schedule": (_c_i64, [ctypes.POINTER(GemmDesc), _PI, _c_int, _c_int, _PI, _PI, _c_i64]),
+    "gps_gemm_diag": (_c_int, [_c_vp, ctypes.POINTER(GemmDesc), _P, _P, _P, _P, _P, _PI, _P, _P,
+                               _PI]),
     "gps_prof_enable": (_c_int, [_c_vp, _c_int]),
     "gps_prof_collect": (_c_int, [_c_vp, _c_cp, _c_i64]),
     "gps_phase_enable": (_c_int, [_c_vp, _c_int]),
@@ -102,6 +127,22 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+def gemm_schedule(desc, kr=None, have_kscale=False, slots=512):
+    """(plan dict, items [n][8]) of one internal GEMM launch (gps_gemm_schedule; no device):
+    item columns wg, ti, tj, k begin, k end, slice, stream-K slot, tickets."""
+    lib = load()
+    plan = np.zeros(len(GEMM_PLAN_NAMES), np.int32)
+    krp = None if kr is None else kr.ctypes.data_as(_PI)
+    pp = plan.ctypes.data_as(_PI)
+    n = lib.gps_gemm_schedule(ctypes.byref(desc), krp, int(have_kscale), slots, pp, None, 0)
+    if n < 0:
+        raise GpsError(lib.gps_last_error(None).decode())
+    items = np.zeros((n, 8), np.int32)
+    lib.gps_gemm_schedule(ctypes.byref(desc), krp, int(have_kscale), slots, pp,
+                          items.ctypes.data_as(_PI), n)
+    return dict(zip(GEMM_PLAN_NAMES, (int(v) for v in plan))), items
 
 
 class GpsError(RuntimeError):
@@ -297,6 +338,16 @@ class Context:
         self.check(0 if rc >= 0 else rc, "gps_ctx_stats")
         return dict(zip(("graphs", "graph_cap", "graph_overflow", "device_bytes", "graph_dropped",
                          "graph_evicted"), (int(v) for v in out)))
+
+    def gemm_diag(self, desc, A, B, C=None, kscale=None, w=None, kr=None, out0=None, out1=None):
+        """One internal GEMM launch on host arrays (gps_gemm_diag; diagnostics): C, out0 and out1
+        are updated in place, the launch launch_gemm chose comes back as a dict (GEMM_PLAN_NAMES)."""
+        plan = np.zeros(len(GEMM_PLAN_NAMES), np.int32)
+        krp = None if kr is None else kr.ctypes.data_as(_PI)
+        self.check(self.lib.gps_gemm_diag(self.h, ctypes.byref(desc), ptr(A), ptr(B), ptr(C),
+                                          ptr(kscale), ptr(w), krp, ptr(out0), ptr(out1),
+                                          plan.ctypes.data_as(_PI)), "gps_gemm_diag")
+        return dict(zip(GEMM_PLAN_NAMES, (int(v) for v in plan)))
 
     def comm_info(self):
         """(nranks, rank, kind) of the context's communicator as the library sees it: RCCL's own

@@ -645,6 +645,62 @@ def test_gemm_layouts(gpu_ctx, ta, tb):
         assert nrel(out, ref) < 1e-13, (M, N, K)
 
 
+@pytest.mark.parametrize("n", [1, 127, 129])
+def test_potrf_potrs_diag_inv_leading_dims(gpu_ctx, n):
+    """Leading dimensions above the logical widths (lda = n + 3, ldb = nrhs + 2, ldx = nrhs + 5):
+    the padding columns of every output keep the caller's sentinel, and gps_potrf leaves
+    A[:, n:lda] as it found it."""
+    from gpscore._lib import ptr
+    rng = np.random.default_rng(100 + n)
+    nrhs, S = 5, -12345.5
+    M = rng.standard_normal((n, n)) / np.sqrt(n)
+    A = M @ M.T + 0.5 * np.eye(n)
+    Lr = np.linalg.cholesky(A)
+    Ap = np.full((n, n + 3), S)
+    Ap[:, :n] = A
+    Bp = np.full((n, nrhs + 2), S)
+    Bp[:, :nrhs] = rng.standard_normal((n, nrhs))
+    X = np.full((n, nrhs + 5), S)
+    gpu_ctx.call("gps_potrs", n, nrhs, ptr(Ap), n + 3, ptr(Bp), nrhs + 2, ptr(X), nrhs + 5)
+    assert nrel(X[:, :nrhs], np.linalg.solve(A, Bp[:, :nrhs])) < 1e-10
+    assert np.array_equal(X[:, nrhs:], np.full((n, 5), S))
+    dinv = np.full(n + 4, S)
+    gpu_ctx.call("gps_diag_inv", n, ptr(Ap), n + 3, ptr(dinv))
+    assert nrel(dinv[:n], np.diag(np.linalg.inv(A))) < 1e-10
+    assert np.array_equal(dinv[n:], np.full(4, S))
+    assert np.array_equal(Ap[:, :n], A) and np.array_equal(Ap[:, n:], np.full((n, 3), S))
+    ld = np.zeros(1)
+    gpu_ctx.call("gps_potrf", n, ptr(Ap), n + 3, ptr(ld))
+    assert nrel(np.tril(Ap[:, :n]), Lr) < 1e-12
+    assert abs(ld[0] - 2 * np.sum(np.log(np.diag(Lr)))) < 1e-10 * n
+    assert np.array_equal(Ap[:, n:], np.full((n, 3), S)), "gps_potrf wrote past column n"
+
+
+def test_gemm_public_padding_path(gpu_ctx):
+    """gps_gemm through its padding path with exact (integer) operands: a shape that reaches the
+    128-tile kernel (2944×2944×16: 529 tiles), ldc > N with sentinel columns that must stay, and
+    beta = 0 over a NaN-filled C, which must not propagate."""
+    from gpscore._lib import ptr
+    rng = np.random.default_rng(77)
+    ints = lambda *s: rng.integers(-4, 5, s).astype(np.float64)
+    A, B = ints(2944, 16), ints(2944, 16)  # B stored [j][k]
+    C = np.full((2944, 2944), np.nan)
+    gpu_ctx.call("gps_gemm", 0, 1, 2944, 2944, 16, 2.0, ptr(A), 16, ptr(B), 16, 0.0, ptr(C), 2944)
+    assert np.array_equal(C, 2.0 * A @ B.T)
+    for (M, N, K) in ((300, 257, 129), (128, 128, 16)):
+        A, B = ints(K, M + 3), ints(K, N + 1)  # A stored [k][i] (lda = M + 3), B [k][j] (ldb = N + 1)
+        C0 = rng.integers(-1000, 1001, (M, N)).astype(np.float64)
+        C = np.full((M, N + 7), 4242.0)
+        C[:, :N] = C0
+        gpu_ctx.call("gps_gemm", 1, 0, M, N, K, -1.0, ptr(A), M + 3, ptr(B), N + 1, 1.0, ptr(C), N + 7)
+        assert np.array_equal(C[:, :N], C0 - A[:, :M].T @ B[:, :N]), (M, N, K)
+        assert np.array_equal(C[:, N:], np.full((M, 7), 4242.0)), (M, N, K)
+        C = np.full((M, N + 7), np.nan)
+        gpu_ctx.call("gps_gemm", 1, 0, M, N, K, 0.5, ptr(A), M + 3, ptr(B), N + 1, 0.0, ptr(C), N + 7)
+        assert np.array_equal(C[:, :N], 0.5 * (A[:, :M].T @ B[:, :N])), (M, N, K)
+        assert np.isnan(C[:, N:]).all()
+
+
 def test_scores_kernel(gpu_ctx):
     from gpscore import compat
     g = load_golden("scores")
