@@ -56,8 +56,9 @@ enum {
  * capacity, gps_comm_info and gps_build_id added; 600: gps_phase_enable / gps_phase_collect /
  * gps_rccl_info added; 700: the joint test predictive, gps_*_predict_cov / _predict_joint /
  * _predict_draws added; 800: the GEMM launch diagnostics gps_gemm_diag / gps_gemm_diag_check /
- * gps_gemm_schedule added).  The binding refuses a mismatch at load. */
-#define GPS_ABI_VERSION 800
+ * gps_gemm_schedule added; 900: the batched small GPs, gps_full_grad_batch / gps_full_train_batch
+ * added).  The binding refuses a mismatch at load. */
+#define GPS_ABI_VERSION 900
 int gps_version(void);
 /* The SHA-256 (hex) of the sources the library was built from (csrc/, this header; computed by
  * gpscore/buildid.py at build time).  Writes at most cap-1 characters and a NUL; returns the
@@ -420,6 +421,41 @@ enum { GPS_SURF_LOGS_ADD_NOISE = 1 };
 int gps_full_surface(gps_ctx* ctx, const double* X, const double* y, int64_t n, int d,
                      double log_sf2, const double* ell, int64_t n_ell, const double* noise_sd,
                      int64_t n_noise, int flags, double* out);
+
+/* ---- batches of small full GPs ----------------------------------
+ * nprob independent full GPs of one shape (n <= 128 training points, d <= 16 inputs, n_ell = 1 or
+ * d, one kind and objective), each with its own data and θ, one workgroup per problem in one
+ * launch — the replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120,
+ * three SGD fits each, SD:192-231 / 277-301 / 372-396) and contour-plot.R's n = 20.  Arrays are
+ * problem-major: X nprob·n·d, y nprob·n, theta nprob·(2 + n_ell).  Both return 0 when the batch
+ * ran, even if some problems failed: info[q] > 0 is the order of the leading minor of problem q
+ * that is not positive definite (a non-finite θ ends there too) and that problem's outputs are
+ * NaN; every other problem is untouched by it.  Results are bitwise independent of nprob and of a
+ * problem's position in the batch.  The resident full-GP / FITC data, any fit and the test
+ * buffers are left as they are (a gps_full_predict afterwards returns what it returned before),
+ * and a communicator does not matter: nothing is sharded. */
+/* Value and gradient (as gps_full_grad) of every problem at its own θ: obj (nprob·GPS_N_OBJ, may
+ * be NULL), grad (nprob·(2 + n_ell)), info (nprob). */
+int gps_full_grad_batch(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* theta, int n_ell,
+                        double* obj, double* grad, int* info);
+/* itr plain SGD steps θ ← θ − lr·grad (KF:254-260) from theta0 on the device, then one forward at
+ * the final kernel parameters: values[q][i] (nprob·itr, may be NULL) is the objective before
+ * step i, thetas[q][i] (nprob·itr·(2 + n_ell), may be NULL) θ after it — the series GP.train
+ * returns — theta_out the final θ, obj (nprob·GPS_N_OBJ, may be NULL) the final objectives.  Xt
+ * (nprob·nt·d; NULL or nt = 0: no predictive) gives mu / var (nprob·nt each, may be NULL) =
+ * k*·α and σ² + sf² − ‖L⁻¹k*‖², and with yt (nprob·nt; NULL: no scores) sc (nprob·GPS_N_SC, may be
+ * NULL) against the problem's own train-target mean and unbiased variance (KF:276-292).  flags
+ * GPS_BATCH_STALE_NOISE: the final pass uses the σ² of the last step's forward (θ0's with itr =
+ * 0) instead of the final one — the scripts' module-global sigma_noise_sq.  A
+ * problem whose factorisation fails stops there: steps_done[q] says how many steps it completed,
+ * its remaining series entries and final outputs are NaN, theta_out[q] is the θ it stopped at. */
+enum { GPS_BATCH_STALE_NOISE = 1 };
+int gps_full_train_batch(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                         const double* y, int64_t n, int d, const double* theta0, int n_ell,
+                         int64_t itr, double lr, const double* Xt, const double* yt, int64_t nt,
+                         int flags, double* theta_out, double* values, double* thetas, double* obj,
+                         double* mu, double* var, double* sc, int* info, int* steps_done);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */
 int gps_comm_unique_id(char uid[128]);

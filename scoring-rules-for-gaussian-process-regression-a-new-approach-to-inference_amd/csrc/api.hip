@@ -685,7 +685,8 @@ std::vector<DBuf*> ctx_buffers(gps_ctx* ctx) {
                  &ctx->bLR, &ctx->bLRv,
                  &ctx->ebuf_aux[0], &ctx->ebuf_aux[1], &ctx->ebuf_aux[2], &ctx->bPIs, &ctx->bRW, &ctx->escale, &ctx->bfv, &ctx->rpart, &ctx->dag_cnt, &ctx->sk_cnt, &ctx->dsig,
                  &ctx->jK, &ctx->jV, &ctx->jslab, &ctx->jS, &ctx->jL, &ctx->jLo, &ctx->jW, &ctx->jvec,
-                 &ctx->jE, &ctx->jdraws, &ctx->jxi, &ctx->jout};
+                 &ctx->jE, &ctx->jdraws, &ctx->jxi, &ctx->jout,
+                 &ctx->btin, &ctx->btstate, &ctx->btint, &ctx->btout};
 }
 
 

@@ -263,8 +263,33 @@ struct SurfaceParams {
   double* out;                       // [4][ns][nl]: LOO-CRPS, in-sample CRPS, NLML, LOO-LogS
 };
 
+// batches of small full GPs, one workgroup per problem (kernels_batch.hip): value + gradient, or
+// `nsteps` SGD steps and, with do_final, the final forward with the test predictive and scores.
+// n <= GPS_SURFACE_MAX_N (the whole matrix in one CU's LDS, as the surface kernel), d <= GPS_BATCH_MAX_D
+#define GPS_BATCH_MAX_D 16
+constexpr int kBatchStepsPerLaunch = 64;  // SGD steps one launch may run
+enum { BATCH_MODE_GRAD = 0, BATCH_MODE_TRAIN = 1 };
+struct BatchParams {
+  const double* x; const double* y;   // [nprob][n][d], [nprob][n]
+  int nprob, n, d, n_ell, kind, objective, mode;
+  // per-problem state, kept on the device between the launches of one call
+  double* theta;      // [nprob][2 + n_ell], read and (training) updated in place
+  double* stale;      // [nprob] log σ² of the last forward a step ran (θ0's before the first)
+  int* info;          // [nprob] 0, or the 1-based order of the leading minor that failed
+  int* steps_done;    // [nprob]
+  int step0, nsteps, itr;   // this launch runs steps [step0, step0 + nsteps) of itr
+  double lr;
+  int do_final, stale_noise;
+  const double* xt; const double* yt; int nt;   // [nprob][nt][d], [nprob][nt]; NULL: none
+  double* values; double* thetas;     // [nprob][itr], [nprob][itr][2 + n_ell]
+  double* obj; double* grad;          // [nprob][GPS_N_OBJ], [nprob][2 + n_ell] (BATCH_MODE_GRAD)
+  double* mu; double* var; double* sc;  // [nprob][nt] twice, [nprob][GPS_N_SC]
+};
+size_t batch_lds_bytes(int n, int d);
+
 // ------------------------------------------------------------------ launchers
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
+hipError_t launch_batch(const BatchParams& p, hipStream_t s);
 hipError_t launch_gram(const GramParams& p, hipStream_t s);
 // C = alpha * op(A) op(B) + beta * C with the epilogue selected by `epi`
 // (info, if given, receives the launch's shape; it changes nothing of the launch)

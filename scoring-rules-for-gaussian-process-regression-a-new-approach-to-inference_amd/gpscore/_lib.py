@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPSCORE_LIB", os.path.join(_HERE, "libgpscore.so"))
-ABI_VERSION = 800  # include/gpscore.h GPS_ABI_VERSION: the signatures below are this version's
+ABI_VERSION = 900  # include/gpscore.h GPS_ABI_VERSION: the signatures below are this version's
 GPS_N_STATS = 6
 GPS_COMM_NONE, GPS_COMM_RCCL, GPS_COMM_LOCAL = 0, 1, 2
 COMM_KINDS = {GPS_COMM_NONE: "none", GPS_COMM_RCCL: "rccl", GPS_COMM_LOCAL: "local"}
@@ -36,6 +36,8 @@ GPS_OPT_AR_CHUNKS = 15
 OBJ_NAMES = ("nlml", "loo_crps", "loo_logs", "logdet", "quad")
 SURFACE_NAMES = ("loo_crps", "insample_crps", "nlml", "loo_logs")
 GPS_SURF_LOGS_ADD_NOISE = 1
+GPS_BATCH_STALE_NOISE = 1
+BATCH_MAX_N, BATCH_MAX_D = 128, 16  # GPS_SURFACE_MAX_N, GPS_BATCH_MAX_D
 SCORE_NAMES = ("test_crps", "test_logs", "test_msll", "test_smse", "test_mse", "test_cover")
 
 _c_int, _c_i64, _c_dbl, _c_vp, _c_cp = (ctypes.c_int, ctypes.c_int64, ctypes.c_double,
@@ -118,6 +120,11 @@ SIGNATURES = {
     "gps_fitc_predict_draws": (_c_int, [_c_vp, _c_i64, _c_i64, _c_int, _P, _P]),
     "gps_full_surface": (_c_int, [_c_vp, _P, _P, _c_i64, _c_int, _c_dbl, _P, _c_i64, _P, _c_i64,
                                   _c_int, _P]),
+    "gps_full_grad_batch": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P,
+                                     _c_int, _P, _P, _PI]),
+    "gps_full_train_batch": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P,
+                                      _c_int, _c_i64, _c_dbl, _P, _P, _c_i64, _c_int, _P, _P, _P,
+                                      _P, _P, _P, _P, _PI, _PI]),
     "gps_comm_unique_id": (_c_int, [_c_cp]),
     "gps_comm_init": (_c_int, [_c_vp, _c_int, _c_int, _c_cp]),
     "gps_comm_init_local": (_c_int, [_c_vp, _c_int, _c_int, ctypes.c_longlong]),

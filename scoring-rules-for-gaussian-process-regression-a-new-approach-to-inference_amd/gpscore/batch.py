@@ -1,0 +1,175 @@
+"""Batches of small full GPs, one workgroup per problem in one launch.
+
+    vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
+    res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
+
+The replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120, three SGD
+fits each: SD:192-231, 277-301, 372-396) and contour-plot.R's n = 20 problems are many tiny,
+independent, sequential fits; here B of them of one shape (n <= 128, d <= 16) run side by side,
+each with its own data and θ.  ``X`` is (B, n, d) or (B, n); ``theta`` is one (log_sf2, log_ell,
+log_sn2) for every problem (log_ell a scalar or length d), or a (B, 2 + n_ell) array with one
+row [log_sf2, log_ell..., log_sn2] per problem.  A problem whose matrix is not positive
+definite does not raise: its ``info`` is the order of the failing leading minor and its outputs
+are NaN; the others are untouched.  Every number comes from libgpscore.so on the GPU.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import (BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
+                   SCORE_NAMES, f64, ptr)
+
+BATCH_OBJS = OBJ_NAMES[:3]  # nlml, loo_crps, loo_logs
+_PI = ctypes.POINTER(ctypes.c_int32)
+
+
+def _iptr(a):
+    return a.ctypes.data_as(_PI)
+
+
+def _problems(X, y):
+    """(X (B, n, d), y (B, n)) checked against the kernel's limits."""
+    try:
+        X, y = f64(X), f64(y)
+    except (ValueError, TypeError) as e:  # a ragged list of problems
+        raise ValueError(f"X and y must be rectangular arrays, one shape per batch: {e}") from None
+    if X.ndim == 2:
+        X = X[:, :, None]
+    if X.ndim != 3 or y.ndim != 2:
+        raise ValueError(f"X must be (B, n, d) or (B, n) and y (B, n), got {X.shape} and {y.shape}")
+    B, n, d = X.shape
+    if y.shape != (B, n):
+        raise ValueError(f"X {X.shape} and y {y.shape} disagree on (B, n)")
+    if B < 1:
+        raise ValueError("the batch is empty")
+    if not 1 <= n <= BATCH_MAX_N:
+        raise ValueError(f"n = {n}: a batched problem holds 1..{BATCH_MAX_N} training points")
+    if not 1 <= d <= BATCH_MAX_D:
+        raise ValueError(f"d = {d}: a batched problem has 1..{BATCH_MAX_D} input dimensions")
+    return np.ascontiguousarray(X), np.ascontiguousarray(y)
+
+
+def _thetas(theta, B, d):
+    """(B, 2 + n_ell) array and n_ell from one (k, ell, noise) or a per-problem array."""
+    if isinstance(theta, (tuple, list)) and len(theta) == 3 and np.ndim(theta[0]) == 0 \
+            and np.ndim(theta[2]) == 0:
+        ell = np.atleast_1d(np.asarray(theta[1], dtype=np.float64)).ravel()
+        row = np.concatenate([[float(theta[0])], ell, [float(theta[2])]])
+        th = np.tile(row, (B, 1))
+    else:
+        try:
+            th = f64(theta)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"theta must be (k, ell, noise) or a (B, 2 + n_ell) array: {e}") from None
+        if th.ndim == 1:
+            th = np.tile(th, (B, 1))
+        if th.ndim != 2 or th.shape[0] != B:
+            raise ValueError(f"theta must be (k, ell, noise) or a (B, 2 + n_ell) array with B = {B}, "
+                             f"got shape {th.shape}")
+    n_ell = th.shape[1] - 2
+    if n_ell not in (1, d):
+        raise ValueError(f"log_ell has {n_ell} entries, expected 1 or d={d}")
+    return np.ascontiguousarray(th), n_ell
+
+
+def _objective(objective):
+    if objective not in BATCH_OBJS:
+        raise ValueError(f"objective must be one of {BATCH_OBJS} (the block-LOO objectives have "
+                         f"no batched path), got {objective!r}")
+    return OBJ_NAMES.index(objective)
+
+
+def value_and_grad_batch(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
+    """Objective value and analytic gradient of B small full GPs at their own θ (one
+    gps_full_grad_batch call; per problem what GP.value_and_grad returns).  Returns
+    (values (B,), grads (B, 2 + n_ell), objectives {name: (B,)}, info (B,))."""
+    X, y = _problems(X, y)
+    B, n, d = X.shape
+    th, n_ell = _thetas(theta, B, d)
+    code = _objective(objective)
+    ctx = ctx or _lib.default_context()
+    obj = np.empty((B, len(OBJ_NAMES)))
+    grad = np.empty((B, 2 + n_ell))
+    info = np.zeros(B, np.int32)
+    ctx.call("gps_full_grad_batch", GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
+             ptr(th), n_ell, ptr(obj), ptr(grad), _iptr(info))
+    objs = {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
+    return objs[objective], grad, objs, info
+
+
+@dataclass
+class BatchTrainResult:
+    """train_batch's outputs, problem-major.  ``theta`` (B, 2 + n_ell) final parameters;
+    ``series`` {"objective": (B, itr) value before each step, "theta": (B, itr, 2 + n_ell)
+    parameters after it} as GP.train; ``objectives`` {name: (B,)} of the final pass; ``mu`` /
+    ``var`` (B, nt) and ``scores`` {name: (B,)} of the test predictive (None without Xt / yt);
+    ``info`` (B,) 0 or the failing leading minor; ``steps_done`` (B,)."""
+    theta: np.ndarray
+    series: dict
+    objectives: dict
+    mu: np.ndarray | None
+    var: np.ndarray | None
+    scores: dict | None
+    info: np.ndarray
+    steps_done: np.ndarray
+
+
+def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
+                stale_noise=False, ctx=None):
+    """The reference's SGD fit loop (`itr` steps θ -= lr·grad, KF:236-260) for B small full GPs
+    at once on the device, then one forward at the final kernel parameters with the test
+    predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score bundle against ``yt`` (B, nt).
+    ``stale_noise``: the final pass uses the noise variance of the last step's forward (θ0's
+    with itr = 0), the scripts' module-global sigma_noise_sq (experiment.run_method)."""
+    X, y = _problems(X, y)
+    B, n, d = X.shape
+    th0, n_ell = _thetas(theta0, B, d)
+    code = _objective(objective)
+    if int(itr) != itr or itr < 0:
+        raise ValueError(f"itr must be a non-negative integer, got {itr!r}")
+    itr = int(itr)
+    lr = float(lr)
+    if not np.isfinite(lr):
+        raise ValueError(f"lr must be finite, got {lr!r}")
+    nt = 0
+    if Xt is not None:
+        try:
+            Xt = f64(Xt)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"Xt must be a rectangular array: {e}") from None
+        if Xt.ndim == 2 and d == 1:
+            Xt = Xt[:, :, None]
+        if Xt.ndim != 3 or Xt.shape[0] != B or Xt.shape[2] != d:
+            raise ValueError(f"Xt must be (B, nt, d) = ({B}, nt, {d}), got {Xt.shape}")
+        Xt = np.ascontiguousarray(Xt)
+        nt = Xt.shape[1]
+        if nt < 1:
+            raise ValueError("Xt holds no rows")
+    if yt is not None:
+        if Xt is None:
+            raise ValueError("yt without Xt")
+        yt = f64(yt)
+        if yt.shape != (B, nt):
+            raise ValueError(f"yt must be (B, nt) = ({B}, {nt}), got {yt.shape}")
+    ctx = ctx or _lib.default_context()
+    nth = 2 + n_ell
+    theta = np.empty((B, nth))
+    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    mu = np.empty((B, nt)) if nt else None
+    var = np.empty((B, nt)) if nt else None
+    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
+    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    ctx.call("gps_full_train_batch", GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
+             ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
+             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(values), ptr(thetas),
+             ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
+    return BatchTrainResult(
+        theta=theta, series={"objective": values, "theta": thetas},
+        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
+        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
+        info=info, steps_done=steps)

@@ -9,8 +9,12 @@ the ±2σ coverage, e.g. KF:267-299).  KIN40K-COMPARE-ALL-FITC-20.py (K20) does 
 a 20-point FITC model whose inducing inputs are trained too, drawing rows without
 reseeding (K20:184-192).
 
+"SIMPLE-DATA FULL-comapre.py" (SD) draws TT = 100 one-dimensional data sets of 120 training
+and 300 test points (SD:158-181) and makes three fits of each from (1, 1, 1) (SD:192-231,
+277-301, 372-396): run_simple sends all replicates of a method through one train_batch call.
+
 Every number here comes from gpscore.GP (libgpscore.so): the SGD loops are GP.train, the
-predictive and its scores GP.predict.  The workbook is not shipped (the scripts open it from
+predictive and its scores GP.predict (run_simple: gpscore.batch.train_batch).  The workbook is not shipped (the scripts open it from
 a Windows drive), so load_sheets reads the .xlsx when pandas has an Excel engine, or the
 same four sheets from an .npz or a directory of <sheet>.csv files.
 """
@@ -23,6 +27,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
+from .batch import train_batch
 from .gp import GP
 
 SHEETS = ("trainx", "trainy", "testx", "testy")
@@ -112,6 +117,12 @@ K20_METHODS = {
     "dss": Method("dss", 3000, 1e-3, 1e-3, z_init="randn", ref="K20:523-593"),
     "kc": Method("kc", 3000, 0.1, 0.1, ref="K20:655-726"),
 }
+# "SIMPLE-DATA FULL-comapre.py": scalar para_l = para_k = para_noise = 1 (SD:203-205), ARD kernel
+SD_METHODS = {
+    "crps": Method("loo_crps", 250, 1.0, init="ones", ref="SD:192-231"),
+    "nlml": Method("nlml", 250, 1e-3, init="ones", ref="SD:277-301"),   # the script's "gp" series
+    "logs": Method("loo_logs", 400, 0.05, init="ones", ref="SD:372-396"),
+}
 
 
 def initial_theta(method, d, rng):
@@ -179,4 +190,55 @@ def run(sheets, TT=30, methods=None, kind="full", itr=None, seed=None, ctx=None,
             r = run_method(gp, data, meth, rng, kind=kind, itr=itr, **kw)
             for k in keys:
                 out[name][k][j] = r[k]
+    return out
+
+
+def simple_data(j, rng=None, num_train=120, num_test=300, num_va=30):
+    """Replicate j of SD's generator (SD:158-181): x = 2·N(0, 1) for num_train + num_test +
+    num_va = 450 points, y one draw of N(0, K + 0.3²I) with K the unit-scale, unit-length
+    squared-exponential kernel, split in that order into train / test / validation.  The
+    script seeds torch with 100·j and draws in float32; here the draws are numpy's, in float64,
+    from ``rng`` (a Generator or a seed; default seed 100·j) — NOT torch's: the same law, other
+    numbers.  The script's own j = 0, 1 data sets are the tests' sd_j* golden files."""
+    rng = np.random.default_rng(100 * j if rng is None else rng)
+    tot = num_train + num_test + num_va
+    x = 2.0 * rng.standard_normal(tot)
+    K = np.exp(-0.5 * (x[:, None] - x[None, :]) ** 2) + 0.3 ** 2 * np.eye(tot)
+    y = np.linalg.cholesky(K) @ rng.standard_normal(tot)
+    a, b = num_train, num_train + num_test
+    return {"train_x": x[:a, None], "train_y": y[:a], "test_x": x[a:b, None], "test_y": y[a:b],
+            "va_x": x[b:, None], "va_y": y[b:]}
+
+
+def run_simple(TT=100, methods=None, datasets=None, itr=None, stale_noise=True, ctx=None):
+    """SD's replicate loop → {method: {metric: array(TT)}} as run: every method's TT fits (its
+    SGD loop, the test predictive and the score bundle) are ONE train_batch call, one
+    workgroup per replicate.  ``datasets``: TT dicts with train_x / train_y / test_x / test_y of
+    one shape (default simple_data(j), j < TT); ``itr`` overrides the methods' step counts;
+    stale_noise as run_method.  A replicate whose factorisation fails raises
+    NotPositiveDefinite, as run_method does for these objectives."""
+    methods = SD_METHODS if methods is None else methods
+    if datasets is None:
+        datasets = [simple_data(j) for j in range(TT)]
+    datasets = list(datasets)
+    if len(datasets) != TT:
+        raise ValueError(f"{len(datasets)} datasets for TT = {TT} replicates")
+    X = np.stack([_as2d(dd["train_x"]) for dd in datasets])
+    y = np.stack([np.asarray(dd["train_y"], np.float64).ravel() for dd in datasets])
+    Xt = np.stack([_as2d(dd["test_x"]) for dd in datasets])
+    yt = np.stack([np.asarray(dd["test_y"], np.float64).ravel() for dd in datasets])
+    d = X.shape[2]
+    out = {}
+    for name, meth in methods.items():
+        th0 = initial_theta(meth, d, None)
+        res = train_batch(X, y, th0, meth.objective, lr=meth.lr,
+                          itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
+                          stale_noise=stale_noise, ctx=ctx)
+        bad = np.flatnonzero(res.info)
+        if bad.size:
+            q = int(bad[0])
+            raise NotPositiveDefinite(int(res.info[q]), f"run_simple: method {name!r}, replicate "
+                                      f"{q}: the leading minor of order {int(res.info[q])} is not "
+                                      f"positive definite after {int(res.steps_done[q])} steps")
+        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
     return out
