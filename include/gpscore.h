@@ -57,7 +57,9 @@ enum {
  * gps_rccl_info added; 700: the joint test predictive, gps_*_predict_cov / _predict_joint /
  * _predict_draws added; 800: the GEMM launch diagnostics gps_gemm_diag / gps_gemm_diag_check /
  * gps_gemm_schedule added; 900: the batched small GPs, gps_full_grad_batch / gps_full_train_batch
- * added).  The binding refuses a mismatch at load. */
+ * added).  gps_fitc_grad_batch / gps_fitc_train_batch joined at 900 without a bump:
+ * they are purely additive, no existing entry point or array changed.  The binding refuses a
+ * mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
 /* The SHA-256 (hex) of the sources the library was built from (csrc/, this header; computed by
@@ -456,6 +458,39 @@ int gps_full_train_batch(gps_ctx* ctx, int kind, int objective, int64_t nprob, c
                          int64_t itr, double lr, const double* Xt, const double* yt, int64_t nt,
                          int flags, double* theta_out, double* values, double* thetas, double* obj,
                          double* mu, double* var, double* sc, int* info, int* steps_done);
+
+/* ---- batches of small FITC GPs -----------------------------------
+ * The FITC sibling of the calls above: nprob independent FITC GPs of one shape (n <= 128 training
+ * points, m <= 32 inducing inputs — m > n is legal —, d <= 16 inputs, n_ell = 1 or d, the ARD
+ * kernel, jitter 1e-3 inside K(Z,Z) as K20:32-39), each with its own data, θ and inducing inputs,
+ * one workgroup per problem — the replicate loops of "SIMPLE-FITC--comapre.py" (TT = 100 data sets
+ * of n = 120 with m = 5, three SGD fits each that move the inducing inputs too, SF:189-237 /
+ * 301-343 / 420-463).  Arrays are problem-major: X nprob·n·d, y nprob·n, Z and grad_z nprob·m·d,
+ * theta nprob·(2 + n_ell).  Both return 0 when the batch ran, even if some problems failed:
+ * info[q] is 0, k in 1..m (the leading minor of order k of K(Z,Z) + 1e-3·I is not positive, a NaN
+ * included) or m + k (the same for B = K(Z,Z) + 1e-3·I + KᵀΛ⁻¹K); a failed problem's outputs are
+ * NaN and every other problem is untouched by it.  Results are bitwise independent of nprob, of a
+ * problem's position in the batch and of how the steps are split over launches.  The resident
+ * data, any fit and the test buffers are left as they are; a communicator does not matter. */
+/* Value and gradient (as gps_fitc_grad) of every problem at its own (θ, Z): obj
+ * (nprob·GPS_N_OBJ, may be NULL), grad (nprob·(2 + n_ell)), grad_z (nprob·m·d), info (nprob). */
+int gps_fitc_grad_batch(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* Z, int m,
+                        const double* theta, int n_ell, double* obj, double* grad, double* grad_z,
+                        int* info);
+/* itr SGD steps θ ← θ − lr·grad, Z ← Z − lr_z·grad_z (SF:229-233) from (theta0, Z0) on the device,
+ * then one forward at the final θ and Z: values / thetas / theta_out / obj / flags as
+ * gps_full_train_batch, z_out (nprob·m·d) the final inducing inputs.  Xt gives mu = k*·c and var
+ * = σ² + sf² − ‖Lm⁻¹k*‖² + ‖Lb⁻¹k*‖², yt the six scores.  A problem whose factorisation fails
+ * stops there: steps_done[q] says how many steps it completed, its remaining series entries and
+ * final outputs are NaN, theta_out[q] / z_out[q] are where it stopped. */
+int gps_fitc_train_batch(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                         const double* y, int64_t n, int d, const double* Z0, int m,
+                         const double* theta0, int n_ell, int64_t itr, double lr, double lr_z,
+                         const double* Xt, const double* yt, int64_t nt, int flags,
+                         double* theta_out, double* z_out, double* values, double* thetas,
+                         double* obj, double* mu, double* var, double* sc, int* info,
+                         int* steps_done);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */
 int gps_comm_unique_id(char uid[128]);

@@ -4,7 +4,8 @@
 // launch helpers, the recursive factorisation driver, L1 blocks), api_full.hip (full GP, CP.R
 // surfaces), api_fitc.hip (FITC fit / gradients / predict), api_block.hip (block-LOO and the
 // energy score), api_joint.hip (the joint test predictive: full covariance, DSS / ES test scores,
-// draws), api_batch.hip (batches of small full GPs, one workgroup each), api_comm.hip (RCCL and the in-process communicator).
+// draws), api_batch.hip (batches of small full GPs, one workgroup each), api_batch_fitc.hip (the
+// same for small FITC GPs), api_comm.hip (RCCL and the in-process communicator).
 #pragma once
 #include <dlfcn.h>
 #include <rccl/rccl.h>

@@ -287,9 +287,33 @@ struct BatchParams {
 };
 size_t batch_lds_bytes(int n, int d);
 
+// batches of small FITC GPs, one workgroup per problem (kernels_batch_fitc.hip): as
+// BatchParams, with m <= GPS_BATCH_FITC_MAX_M inducing inputs per problem that the SGD steps move
+// too (z -= lr_z·∂/∂z).  ARD kernel only, jitter 1e-3 inside K̃mm (K20:32-39).
+#define GPS_BATCH_FITC_MAX_M 32
+struct BatchFitcParams {
+  const double* x; const double* y;   // [nprob][n][d], [nprob][n]
+  int nprob, n, d, m, n_ell, objective, mode;
+  // per-problem state, kept on the device between the launches of one call
+  double* theta;      // [nprob][2 + n_ell], read and (training) updated in place
+  double* z;          // [nprob][m][d], read and (training) updated in place
+  double* stale;      // [nprob] log σ² of the last forward a step ran (θ0's before the first)
+  int* info;          // [nprob] 0, k (K̃mm's leading minor k failed) or m + k (B's)
+  int* steps_done;    // [nprob]
+  int step0, nsteps, itr;   // this launch runs steps [step0, step0 + nsteps) of itr
+  double lr, lr_z;
+  int do_final, stale_noise;
+  const double* xt; const double* yt; int nt;   // [nprob][nt][d], [nprob][nt]; NULL: none
+  double* values; double* thetas;     // [nprob][itr], [nprob][itr][2 + n_ell]
+  double* obj; double* grad; double* grad_z;  // [nprob][GPS_N_OBJ]; BATCH_MODE_GRAD: [nprob][2 + n_ell], [nprob][m][d]
+  double* mu; double* var; double* sc;  // [nprob][nt] twice, [nprob][GPS_N_SC]
+};
+size_t batch_fitc_lds_bytes(int n, int m, int d);
+
 // ------------------------------------------------------------------ launchers
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 hipError_t launch_batch(const BatchParams& p, hipStream_t s);
+hipError_t launch_batch_fitc(const BatchFitcParams& p, hipStream_t s);
 hipError_t launch_gram(const GramParams& p, hipStream_t s);
 // C = alpha * op(A) op(B) + beta * C with the epilogue selected by `epi`
 // (info, if given, receives the launch's shape; it changes nothing of the launch)

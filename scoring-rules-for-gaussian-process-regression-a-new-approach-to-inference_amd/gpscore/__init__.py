@@ -5,13 +5,15 @@ the FITC sparse GP (Woodbury form, rows sharded over GPUs with RCCL).
 Drop-in layers:
   * ``gpscore.compat``  — the reference scripts' helper functions, same names;
   * ``gpscore.GP``      — fit / predict / score on numpy arrays;
-  * ``gpscore.batch``   — many small full GPs (n <= 128) valued, trained and scored in one launch;
+  * ``gpscore.batch``   — many small full GPs (n <= 128), or small FITC GPs (n <= 128, m <= 32,
+                          the inducing inputs trained too), valued, trained and scored in one launch;
   * ``gpscore.dist``    — one process per GPU, FITC row sharding;
   * ``gpscore._lib``    — the ctypes binding of libgpscore.so (include/gpscore.h).
 """
 from ._lib import (Context, GpsError, NotPositiveDefinite, build_id, check_build_id,  # noqa: F401
                    default_context, load, OBJ_NAMES, SCORE_NAMES)
 from .gp import GP, FitResult, fit, pack_theta, score, surface  # noqa: F401
-from .batch import BatchTrainResult, train_batch, value_and_grad_batch  # noqa: F401
+from .batch import (BatchTrainResult, FitcBatchTrainResult, fitc_train_batch,  # noqa: F401
+                    fitc_value_and_grad_batch, train_batch, value_and_grad_batch)
 
 __version__ = "0.1.0"

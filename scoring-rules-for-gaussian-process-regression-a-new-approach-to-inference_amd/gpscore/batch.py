@@ -1,7 +1,11 @@
-"""Batches of small full GPs, one workgroup per problem in one launch.
+"""Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
+(DESIGN §19, §20).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
+    vals, grads, gZ, objs, info = gpscore.fitc_value_and_grad_batch(X, y, Z, theta, "loo_crps")
+    res = gpscore.fitc_train_batch(X, y, Z0, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, lr_z=1.0,
+                                   itr=1000, Xt=Xt, yt=yt)
 
 The replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120, three SGD
 fits each: SD:192-231, 277-301, 372-396) and contour-plot.R's n = 20 problems are many tiny,
@@ -11,6 +15,13 @@ log_sn2) for every problem (log_ell a scalar or length d), or a (B, 2 + n_ell) a
 row [log_sf2, log_ell..., log_sn2] per problem.  A problem whose matrix is not positive
 definite does not raise: its ``info`` is the order of the failing leading minor and its outputs
 are NaN; the others are untouched.  Every number comes from libgpscore.so on the GPU.
+
+The FITC calls do the same for the replicate loops of "SIMPLE-FITC--comapre.py" (TT = 100 data
+sets of n = 120 with m = 5 inducing inputs, three SGD fits each that move the inducing inputs
+too: SF:189-237, 301-343, 420-463): ``Z`` is (B, m, d), or (B, m) when d = 1, with m <= 32 (m > n
+is legal); the ARD kernel with the 1e-3 jitter inside K(Z,Z) as the resident FITC path.  There
+``info`` is k in 1..m when the leading minor of order k of K(Z,Z) + 1e-3·I fails and m + k when
+that of B = K(Z,Z) + 1e-3·I + KᵀΛ⁻¹K does.
 """
 from __future__ import annotations
 
@@ -20,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
+from ._lib import (BATCH_FITC_MAX_M, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
                    SCORE_NAMES, f64, ptr)
 
 BATCH_OBJS = OBJ_NAMES[:3]  # nlml, loo_crps, loo_logs
@@ -118,23 +129,17 @@ class BatchTrainResult:
     steps_done: np.ndarray
 
 
-def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
-                stale_noise=False, ctx=None):
-    """The reference's SGD fit loop (`itr` steps θ -= lr·grad, KF:236-260) for B small full GPs
-    at once on the device, then one forward at the final kernel parameters with the test
-    predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score bundle against ``yt`` (B, nt).
-    ``stale_noise``: the final pass uses the noise variance of the last step's forward (θ0's
-    with itr = 0), the scripts' module-global sigma_noise_sq (experiment.run_method)."""
-    X, y = _problems(X, y)
-    B, n, d = X.shape
-    th0, n_ell = _thetas(theta0, B, d)
-    code = _objective(objective)
+def _steps(itr, lr):
     if int(itr) != itr or itr < 0:
         raise ValueError(f"itr must be a non-negative integer, got {itr!r}")
-    itr = int(itr)
     lr = float(lr)
     if not np.isfinite(lr):
         raise ValueError(f"lr must be finite, got {lr!r}")
+    return int(itr), lr
+
+
+def _tests(Xt, yt, B, d):
+    """(Xt (B, nt, d) or None, yt (B, nt) or None, nt) checked against the batch."""
     nt = 0
     if Xt is not None:
         try:
@@ -155,6 +160,22 @@ def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt
         yt = f64(yt)
         if yt.shape != (B, nt):
             raise ValueError(f"yt must be (B, nt) = ({B}, {nt}), got {yt.shape}")
+    return Xt, yt, nt
+
+
+def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
+                stale_noise=False, ctx=None):
+    """The reference's SGD fit loop (`itr` steps θ -= lr·grad, KF:236-260) for B small full GPs
+    at once on the device, then one forward at the final kernel parameters with the test
+    predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score bundle against ``yt`` (B, nt).
+    ``stale_noise``: the final pass uses the noise variance of the last step's forward (θ0's
+    with itr = 0), the scripts' module-global sigma_noise_sq (experiment.run_method)."""
+    X, y = _problems(X, y)
+    B, n, d = X.shape
+    th0, n_ell = _thetas(theta0, B, d)
+    code = _objective(objective)
+    itr, lr = _steps(itr, lr)
+    Xt, yt, nt = _tests(Xt, yt, B, d)
     ctx = ctx or _lib.default_context()
     nth = 2 + n_ell
     theta = np.empty((B, nth))
@@ -173,3 +194,83 @@ def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt
         objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
         scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
         info=info, steps_done=steps)
+
+
+def _inducing(Z, B, d):
+    """Z (B, m, d) checked against the batch and the kernel's limit."""
+    try:
+        Z = f64(Z)
+    except (ValueError, TypeError) as e:  # a ragged list of inducing sets
+        raise ValueError(f"Z must be a rectangular array, one m per batch: {e}") from None
+    if Z.ndim == 2 and d == 1:
+        Z = Z[:, :, None]
+    if Z.ndim != 3 or Z.shape[0] != B or Z.shape[2] != d:
+        raise ValueError(f"Z must be (B, m, d) = ({B}, m, {d}) (or (B, m) when d = 1), got {Z.shape}")
+    m = Z.shape[1]
+    if not 1 <= m <= BATCH_FITC_MAX_M:
+        raise ValueError(f"m = {m}: a batched FITC problem holds 1..{BATCH_FITC_MAX_M} inducing "
+                         f"inputs")
+    return np.ascontiguousarray(Z), m
+
+
+def fitc_value_and_grad_batch(X, y, Z, theta, objective="loo_crps", ctx=None):
+    """Objective value and analytic gradient of B small FITC GPs at their own (θ, Z) (one
+    gps_fitc_grad_batch call; per problem what GP.value_and_grad(..., Z=Z) returns).  Returns
+    (values (B,), grads (B, 2 + n_ell), grad_Z (B, m, d), objectives {name: (B,)}, info (B,))."""
+    X, y = _problems(X, y)
+    B, n, d = X.shape
+    Z, m = _inducing(Z, B, d)
+    th, n_ell = _thetas(theta, B, d)
+    code = _objective(objective)
+    ctx = ctx or _lib.default_context()
+    obj = np.empty((B, len(OBJ_NAMES)))
+    grad = np.empty((B, 2 + n_ell))
+    gz = np.empty((B, m, d))
+    info = np.zeros(B, np.int32)
+    ctx.call("gps_fitc_grad_batch", code, B, ptr(X), ptr(y), n, d, ptr(Z), m, ptr(th), n_ell,
+             ptr(obj), ptr(grad), ptr(gz), _iptr(info))
+    objs = {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
+    return objs[objective], grad, gz, objs, info
+
+
+@dataclass
+class FitcBatchTrainResult(BatchTrainResult):
+    """fitc_train_batch's outputs: BatchTrainResult's fields and ``Z`` (B, m, d), the final
+    inducing inputs.  ``info`` is 0, k in 1..m (K(Z,Z) + 1e-3·I's leading minor) or m + k (B's)."""
+    Z: np.ndarray = None
+
+
+def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, itr=400, Xt=None,
+                     yt=None, stale_noise=False, ctx=None):
+    """The SGD fit loop of the FITC scripts (`itr` steps θ -= lr·grad, Z -= lr_z·grad_Z,
+    SF:229-233; lr_z defaults to lr) for B small FITC GPs at once on the device, then one forward
+    at the final θ and Z with the test predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score
+    bundle against ``yt`` (B, nt).  ``stale_noise`` as train_batch."""
+    X, y = _problems(X, y)
+    B, n, d = X.shape
+    Z0, m = _inducing(Z0, B, d)
+    th0, n_ell = _thetas(theta0, B, d)
+    code = _objective(objective)
+    itr, lr = _steps(itr, lr)
+    lr_z = lr if lr_z is None else float(lr_z)
+    if not np.isfinite(lr_z):
+        raise ValueError(f"lr_z must be finite, got {lr_z!r}")
+    Xt, yt, nt = _tests(Xt, yt, B, d)
+    ctx = ctx or _lib.default_context()
+    nth = 2 + n_ell
+    theta, Z = np.empty((B, nth)), np.empty((B, m, d))
+    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    mu = np.empty((B, nt)) if nt else None
+    var = np.empty((B, nt)) if nt else None
+    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
+    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    ctx.call("gps_fitc_train_batch", code, B, ptr(X), ptr(y), n, d, ptr(Z0), m, ptr(th0), n_ell,
+             itr, lr, lr_z, ptr(Xt), ptr(yt), nt, GPS_BATCH_STALE_NOISE if stale_noise else 0,
+             ptr(theta), ptr(Z), ptr(values), ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc),
+             _iptr(info), _iptr(steps))
+    return FitcBatchTrainResult(
+        theta=theta, series={"objective": values, "theta": thetas},
+        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
+        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
+        info=info, steps_done=steps, Z=Z)

@@ -12,6 +12,9 @@ reseeding (K20:184-192).
 "SIMPLE-DATA FULL-comapre.py" (SD) draws TT = 100 one-dimensional data sets of 120 training
 and 300 test points (SD:158-181) and makes three fits of each from (1, 1, 1) (SD:192-231,
 277-301, 372-396): run_simple sends all replicates of a method through one train_batch call.
+"SIMPLE-FITC--comapre.py" (SF) fits the same data sets with a FITC model of m = 5 inducing inputs
+that are trained too (SF:189-237, 301-343, 420-463): run_simple_fitc, one fitc_train_batch call
+per method.
 
 Every number here comes from gpscore.GP (libgpscore.so): the SGD loops are GP.train, the
 predictive and its scores GP.predict (run_simple: gpscore.batch.train_batch).  The workbook is not shipped (the scripts open it from
@@ -27,7 +30,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
-from .batch import train_batch
+from .batch import fitc_train_batch, train_batch
 from .gp import GP
 
 SHEETS = ("trainx", "trainy", "testx", "testy")
@@ -122,6 +125,12 @@ SD_METHODS = {
     "crps": Method("loo_crps", 250, 1.0, init="ones", ref="SD:192-231"),
     "nlml": Method("nlml", 250, 1e-3, init="ones", ref="SD:277-301"),   # the script's "gp" series
     "logs": Method("loo_logs", 400, 0.05, init="ones", ref="SD:372-396"),
+}
+# "SIMPLE-FITC--comapre.py": the same start, m = 5 inducing inputs with their own step lr_z
+SF_METHODS = {
+    "crps": Method("loo_crps", 1000, 1.0, 1.0, init="ones", ref="SF:189-237"),
+    "nlml": Method("nlml", 1200, 5e-4, 5e-3, init="ones", ref="SF:301-343"),   # the "gp" series
+    "logs": Method("loo_logs", 2500, 5e-3, 5e-3, init="ones", ref="SF:420-463"),
 }
 
 
@@ -241,4 +250,55 @@ def run_simple(TT=100, methods=None, datasets=None, itr=None, stale_noise=True, 
                                       f"{q}: the leading minor of order {int(res.info[q])} is not "
                                       f"positive definite after {int(res.steps_done[q])} steps")
         out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
+    return out
+
+
+def simple_inducing(j, rng=None, m=5, d=1):
+    """Replicate j's starting inducing inputs as SF:200 draws them, torch.randint(-3, 3, (m, d)):
+    integers uniform in {-3, ..., 2}, as float64.  The draws are numpy's from ``rng`` (a Generator
+    or a seed; default seed 100·j + 1), NOT torch's — the same caveat as simple_data.  Duplicates
+    are expected and legal: the 1e-3 jitter keeps K(Z,Z) + 1e-3·I positive definite."""
+    rng = np.random.default_rng(100 * j + 1 if rng is None else rng)
+    return rng.integers(-3, 3, size=(m, d)).astype(np.float64)
+
+
+def run_simple_fitc(TT=100, methods=None, datasets=None, Z0=None, itr=None, stale_noise=True,
+                    ctx=None):
+    """SF's replicate loop → {method: {metric: array(TT), "Z": array(TT, m, d)}}: every method's
+    TT FITC fits (its SGD loop over θ and the inducing inputs, the test predictive and the score
+    bundle) are ONE fitc_train_batch call, one workgroup per replicate.  ``datasets`` as
+    run_simple; ``Z0``: (TT, m, d) starting inducing inputs (default simple_inducing(j), j < TT),
+    the same for every method; ``itr`` overrides the methods' step counts; stale_noise as
+    run_method.  A replicate whose factorisation fails raises NotPositiveDefinite."""
+    methods = SF_METHODS if methods is None else methods
+    if datasets is None:
+        datasets = [simple_data(j) for j in range(TT)]
+    datasets = list(datasets)
+    if len(datasets) != TT:
+        raise ValueError(f"{len(datasets)} datasets for TT = {TT} replicates")
+    X = np.stack([_as2d(dd["train_x"]) for dd in datasets])
+    y = np.stack([np.asarray(dd["train_y"], np.float64).ravel() for dd in datasets])
+    Xt = np.stack([_as2d(dd["test_x"]) for dd in datasets])
+    yt = np.stack([np.asarray(dd["test_y"], np.float64).ravel() for dd in datasets])
+    d = X.shape[2]
+    if Z0 is None:
+        Z0 = np.stack([simple_inducing(j, d=d) for j in range(TT)])
+    Z0 = np.asarray(Z0, np.float64)
+    if Z0.shape[0] != TT:
+        raise ValueError(f"Z0 holds {Z0.shape[0]} inducing sets for TT = {TT} replicates")
+    out = {}
+    for name, meth in methods.items():
+        th0 = initial_theta(meth, d, None)
+        res = fitc_train_batch(X, y, Z0, th0, meth.objective, lr=meth.lr, lr_z=meth.lr_z,
+                               itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
+                               stale_noise=stale_noise, ctx=ctx)
+        bad = np.flatnonzero(res.info)
+        if bad.size:
+            q = int(bad[0])
+            raise NotPositiveDefinite(int(res.info[q]), f"run_simple_fitc: method {name!r}, "
+                                      f"replicate {q}: info = {int(res.info[q])} (k: the leading "
+                                      f"minor of order k of K(Z,Z) + 1e-3 I, m + k: of B) after "
+                                      f"{int(res.steps_done[q])} steps")
+        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
+        out[name]["Z"] = res.Z.copy()
     return out
