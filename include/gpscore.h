@@ -58,7 +58,8 @@ enum {
  * _predict_draws added; 800: the GEMM launch diagnostics gps_gemm_diag / gps_gemm_diag_check /
  * gps_gemm_schedule added; 900: the batched small GPs, gps_full_grad_batch / gps_full_train_batch
  * added).  gps_fitc_grad_batch / gps_fitc_train_batch joined at 900 without a bump:
- * they are purely additive, no existing entry point or array changed.  The binding refuses a
+ * they are purely additive, no existing entry point or array changed; so did gps_potrf_diag
+ * (DESIGN §21).  The binding refuses a
  * mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -228,6 +229,23 @@ int gps_gemm_diag(gps_ctx* ctx, const gps_gemm_desc* d, const double* A, const d
  * count, -1 on a refused description.  Needs no device. */
 int64_t gps_gemm_schedule(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int slots,
                           int32_t* plan, int32_t* items, int64_t cap);
+
+/* Diagnostics: the factorisation with its fused inverse as gps_potrf runs it (the same upload,
+ * buffers, options, graph capture and replay), everything it wrote copied back whole
+ * (tests/test_gpu_factor.py).  With n_pad = n rounded up to 128: L and Linv take the
+ * padded n_pad × n_pad squares (row stride n_pad) — the upper parts the kernels never write and
+ * the identity padding included — and logdiag the n_pad values log L_ii.  *info is 0 or the first
+ * non-positive-definite leading minor; the call RETURNS 0 in both cases (the launches complete
+ * on a bad pivot, the factors hold NaNs from there on), -1 on a bad argument (NULL, n <= 0,
+ * lda < n; nothing is launched), other negatives as everywhere.  plan[GPS_N_POTRF_PLAN]: what
+ * ran — n_pad, stand-alone 128-leaf launches, persistent launches with their smallest and largest
+ * block (in tiles; 0 without one), the recursion's GEMM launches, and 1 if the sequence was
+ * replayed from a cached graph (the counts then are those of its capture). */
+enum { GPS_POTRF_PLAN_NPAD = 0, GPS_POTRF_PLAN_LEAVES = 1, GPS_POTRF_PLAN_DAGS = 2,
+       GPS_POTRF_PLAN_DAG_TMIN = 3, GPS_POTRF_PLAN_DAG_TMAX = 4, GPS_POTRF_PLAN_GEMMS = 5,
+       GPS_POTRF_PLAN_REPLAYED = 6, GPS_N_POTRF_PLAN = 8 };
+int gps_potrf_diag(gps_ctx* ctx, int64_t n, const double* A, int64_t lda, double* L, double* Linv,
+                   double* logdiag, int32_t* info, int32_t* plan);
 
 /* on: 0 off, 1 per-kernel-class tags, 2 GEMM tags also carry layout/shape/tri/split-K/lda */
 int gps_prof_enable(gps_ctx* ctx, int on);

@@ -336,6 +336,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
   if (nb == 1) {
     Prof pr(ctx, "potrf_diag128", 2.0 * 128 * 128 * 128 / 3.0, 0);
     HIPCHK(launch_potrf_leaf(A, lda, Linv, ldl, Lout, ldlo, logdiag, info, base, nreal, s));
+    ++ctx->fplan.leaves;
     return 0;
   }
   if (dag_block(ctx, nb)) {  // the whole block in one persistent launch (kernels_potrf.hip)
@@ -356,6 +357,10 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     const double nn = 128.0 * nb;
     Prof pr(ctx, "potrf_dag", 2.0 * nn * nn * nn / 3.0, 0);
     HIPCHK(launch_potrf_dag(d, dag_width(ctx, nb, ctx->dag_half), s));
+    gps_ctx::FactorPlan& fp = ctx->fplan;
+    fp.dag_tmin = fp.dags ? std::min(fp.dag_tmin, nb) : nb;
+    fp.dag_tmax = std::max(fp.dag_tmax, nb);
+    ++fp.dags;
     return 0;
   }
   const int n1b = nb / 2, n2b = nb - n1b;
@@ -400,6 +405,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     p.A = A21; p.lda = lda; p.B = Linv; p.ldb = ldl; p.C = W; p.ldc = n1;
     p.M = n2; p.N = n1; p.K = n1; p.tri = TRI_K_LE_J;
     if ((rc = gemm(ctx, LAY_N, LAY_T, EPI_STORE, p))) return rc;
+    ++ctx->fplan.gemms;
   }
   if (Lout) HIPCHK(hipMemcpy2DAsync(Lout + (int64_t)n1 * ldlo, ldlo * 8, W, (size_t)n1 * 8,
                                     (size_t)n1 * 8, n2, hipMemcpyDeviceToDevice, s));
@@ -419,12 +425,14 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     p.M = n2; p.N = n2; p.K = n1; p.alpha = -1.0; p.beta = 1.0; p.lower_out = 1;
     p.sk_alone = forked ? 0 : 1;
     if ((rc = gemm(ctx, LAY_N, LAY_T, EPI_STORE, p))) return rc;
+    ++ctx->fplan.gemms;
   }
   {  // T = L21 · L11⁻¹ → A21 (off the critical path)
     GemmParams p = gp0();
     p.A = W; p.lda = n1; p.B = Linv; p.ldb = ldl; p.C = A21; p.ldc = lda;
     p.M = n2; p.N = n1; p.K = n1; p.tri = TRI_K_GE_J;
     if ((rc = gemm(ctx, LAY_N, LAY_N, EPI_STORE, p, ts))) return rc;
+    ++ctx->fplan.gemms;
   }
   if (forked) HIPCHK(hipEventRecord(join, ts));
   // top level with a pre-pass request: L11⁻¹ is final now, so the product that needs only its
@@ -454,6 +462,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     p.A = Li22; p.lda = ldl; p.B = A21; p.ldb = lda; p.C = Li21; p.ldc = ldl;
     p.M = n2; p.N = n1; p.K = n2; p.alpha = -1.0; p.tri = TRI_K_LE_I;
     if ((rc = gemm(ctx, LAY_N, LAY_N, EPI_STORE, p))) return rc;
+    ++ctx->fplan.gemms;
   }
   if (top && ctx->pre.join) {
     HIPCHK(hipStreamWaitEvent(s, ctx->pre.join, 0));
@@ -537,6 +546,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
     ctx->sync_used = 0;
     ctx->pre.join = nullptr;
     ctx->dag_cnt_used = 0;
+    ctx->fplan = gps_ctx::FactorPlan{};
     return potrf_inv_rec(ctx, A, n_pad, Linv, n_pad, W, (int)(n_pad / GPS_TILE), logdiag,
                          static_cast<int*>(ctx->info.p), 0, nreal, Lout, n_pad, true);
   };
@@ -563,6 +573,8 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
     if (g.key == key) {
       g.last_use = ++ctx->graph_tick;
       HIPCHK(hipGraphLaunch(g.exec, ctx->stream));
+      ctx->fplan = g.plan;
+      ctx->fplan.replayed = 1;
       return 0;
     }
   // Full cache: the least recently used exec is destroyed (after the context's streams drain).
@@ -598,7 +610,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
   const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
   (void)hipGraphDestroy(graph);
   HIPCHK(ei);
-  ctx->pgraphs.push_back({key, exec, ++ctx->graph_tick});
+  ctx->pgraphs.push_back({key, exec, ++ctx->graph_tick, ctx->fplan});
   HIPCHK(hipGraphLaunch(exec, ctx->stream));
   return 0;
 }

@@ -1,6 +1,8 @@
 // Diagnostics of the GEMM launcher (include/gpscore.h: gps_gemm_diag / gps_gemm_diag_check): one
 // internal launch on host arrays, so the tests can drive every kernel variant alone and compare
-// it exactly (tests/test_gpu_gemm_modes.py).  Nothing here is on a production path.
+// it exactly (tests/test_gpu_gemm_modes.py); and of the factorisation
+// (gps_potrf_diag): gps_potrf's own path with every buffer it wrote copied back whole
+// (tests/test_gpu_factor.py).  Nothing here is on a production path.
 #include "api_internal.h"
 
 // (the binding's ctypes structure is checked against the same size: tests/test_gemm_diag_args.py)
@@ -207,6 +209,30 @@ int gps_gemm_diag(gps_ctx* ctx, const gps_gemm_desc* d, const double* A, const d
   const int v[GPS_N_GEMM_PLAN] = {info.tile, info.ksplit, info.map_mode, info.sk_dp,
                                   info.sk_wgs, info.slab_xcd, info.grid_x, info.grid_y};
   for (int i = 0; i < GPS_N_GEMM_PLAN; ++i) plan[i] = v[i];
+  return 0;
+}
+
+int gps_potrf_diag(gps_ctx* ctx, int64_t n, const double* A, int64_t lda, double* L, double* Linv,
+                   double* logdiag, int32_t* info, int32_t* plan) {
+  // judged first, before anything touches the device
+  if (!A || !L || !Linv || !logdiag || !info || !plan)
+    return fail(ctx, -1, "gps_potrf_diag: NULL argument");
+  if (n <= 0 || lda < n || n > (1 << 20)) return fail(ctx, -1, "gps_potrf_diag: bad shape");
+  if (int rc = bind(ctx)) return rc;
+  // gps_potrf's own path: the same buffers, options, capture and replay
+  const int rc = factor_user(ctx, n, A, lda, true);
+  if (rc < 0) return rc;
+  *info = rc;  // 0, or the first non-PD minor (the launches completed; NaNs from that pivot on)
+  const int64_t np = pad_to(n);
+  hipStream_t s = ctx->stream;
+  HIPCHK(hipMemcpyAsync(logdiag, ctx->t4.d(), (size_t)np * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(L, ctx->t4.d() + np, (size_t)np * np * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(Linv, ctx->t2.d(), (size_t)np * np * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const gps_ctx::FactorPlan& fp = ctx->fplan;
+  const int v[GPS_N_POTRF_PLAN] = {(int)np, fp.leaves, fp.dags, fp.dag_tmin, fp.dag_tmax, fp.gemms,
+                                   fp.replayed, 0};
+  for (int i = 0; i < GPS_N_POTRF_PLAN; ++i) plan[i] = v[i];
   return 0;
 }
 

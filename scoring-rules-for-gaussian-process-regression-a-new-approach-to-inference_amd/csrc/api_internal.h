@@ -153,10 +153,16 @@ struct gps_ctx {
     int* sig = nullptr;                // row signals: the pre-pass runs behind the L11 block
                                        // (GPS_OPT_FITC_DEP; zeroed by the caller)
   } pre;
+  struct FactorPlan {                  // what the last potrf_inv ran (gps_potrf_diag): stand-alone
+    int leaves = 0, dags = 0;          // leaf launches, persistent launches with their smallest
+    int dag_tmin = 0, dag_tmax = 0;    // and largest T, the recursion's GEMM launches, and whether
+    int gemms = 0, replayed = 0;       // the sequence was replayed from a cached graph
+  } fplan;
   struct PotrfGraph {                  // one captured potrf_inv launch sequence
     std::vector<uintptr_t> key;
     hipGraphExec_t exec = nullptr;
     uint64_t last_use = 0;
+    FactorPlan plan;                   // the launches it holds
   };
   std::vector<PotrfGraph> pgraphs;     // keyed by buffers, sizes, streams, options; least recently
                                        // used evicted past kMaxGraphs; dropped with their buffers

@@ -64,6 +64,9 @@ class GemmDesc(ctypes.Structure):
 
 
 GEMM_PLAN_NAMES = ("tile", "ksplit", "map_mode", "sk_dp", "sk_wgs", "slab_xcd", "grid_x", "grid_y")
+# gps_potrf_diag's plan (GPS_POTRF_PLAN_*; the last word is reserved)
+POTRF_PLAN_NAMES = ("n_pad", "leaves", "dags", "dag_tmin", "dag_tmax", "gemms", "replayed",
+                    "reserved")
 
 # name -> (restype, argtypes); every symbol include/gpscore.h declares
 SIGNATURES = {
@@ -83,6 +86,7 @@ SIGNATURES = {
     "gps_gemm_schedule": (_c_i64, [ctypes.POINTER(GemmDesc), _PI, _c_int, _c_int, _PI, _PI, _c_i64]),
     "gps_gemm_diag": (_c_int, [_c_vp, ctypes.POINTER(GemmDesc), _P, _P, _P, _P, _P, _PI, _P, _P,
                                _PI]),
+    "gps_potrf_diag": (_c_int, [_c_vp, _c_i64, _P, _c_i64, _P, _P, _P, _PI, _PI]),
     "gps_prof_enable": (_c_int, [_c_vp, _c_int]),
     "gps_prof_collect": (_c_int, [_c_vp, _c_cp, _c_i64]),
     "gps_phase_enable": (_c_int, [_c_vp, _c_int]),
@@ -361,6 +365,24 @@ class Context:
                                           ptr(kscale), ptr(w), krp, ptr(out0), ptr(out1),
                                           plan.ctypes.data_as(_PI)), "gps_gemm_diag")
         return dict(zip(GEMM_PLAN_NAMES, (int(v) for v in plan)))
+
+    def potrf_diag(self, A):
+        """The factorisation as gps_potrf runs it, everything it wrote copied back whole
+        (gps_potrf_diag; diagnostics): (L, Linv, logdiag, info, plan) with L and Linv the padded
+        n_pad x n_pad squares, info 0 or the first non-PD minor (no exception), plan a dict
+        (POTRF_PLAN_NAMES)."""
+        A = f64(A)
+        n = A.shape[0]
+        npad = (n + 127) // 128 * 128
+        L = np.full((npad, npad), np.nan)
+        Li = np.full((npad, npad), np.nan)
+        ld = np.full(npad, np.nan)
+        info = np.full(1, -1, np.int32)
+        plan = np.zeros(len(POTRF_PLAN_NAMES), np.int32)
+        self.check(self.lib.gps_potrf_diag(self.h, n, ptr(A), A.shape[1], ptr(L), ptr(Li), ptr(ld),
+                                           info.ctypes.data_as(_PI), plan.ctypes.data_as(_PI)),
+                   "gps_potrf_diag")
+        return L, Li, ld, int(info[0]), dict(zip(POTRF_PLAN_NAMES, (int(v) for v in plan)))
 
     def comm_info(self):
         """(nranks, rank, kind) of the context's communicator as the library sees it: RCCL's own
