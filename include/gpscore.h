@@ -59,7 +59,7 @@ enum {
  * gps_gemm_schedule added; 900: the batched small GPs, gps_full_grad_batch / gps_full_train_batch
  * added).  gps_fitc_grad_batch / gps_fitc_train_batch joined at 900 without a bump:
  * they are purely additive, no existing entry point or array changed; so did gps_potrf_diag
- * (DESIGN §21).  The binding refuses a
+ *  and gps_fitc_grad_tall / gps_fitc_train_tall.  The binding refuses a
  * mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -509,6 +509,28 @@ int gps_fitc_train_batch(gps_ctx* ctx, int objective, int64_t nprob, const doubl
                          double* theta_out, double* z_out, double* values, double* thetas,
                          double* obj, double* mu, double* var, double* sc, int* info,
                          int* steps_done);
+
+/* ---- batches of tall FITC GPs -------------------------------------
+ * gps_fitc_grad_batch / gps_fitc_train_batch for 1 <= n <= 2048 training points: the same argument
+ * lists, model (m <= 32, d <= 16, n_ell = 1 or d, ARD, jitter 1e-3), outputs, info codes, failure
+ * semantics and bitwise independence of nprob, position and launch split — the replicate loops of
+ * "KIN40K-COMPARE-ALL-FITC-20" (n = 500, d = 8, m = 20; LOO-CRPS 2000, NLML 3000, LOO-LogS 3000
+ * steps).  One workgroup per problem as there, with V, U and the n-vectors in a per-problem
+ * device workspace of the call's own instead of LDS; a launch runs max(1, 64 / ceil(n / 128))
+ * steps.  They agree with the small-batch calls within rounding, never bitwise; for n <= 128 the
+ * small-batch calls are the faster route.  A batch whose inputs, outputs or workspace
+ * (nprob·(2n(m|1) + 9n) doubles) exceed 8 GiB is refused. */
+int gps_fitc_grad_tall(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                       const double* y, int64_t n, int d, const double* Z, int m,
+                       const double* theta, int n_ell, double* obj, double* grad, double* grad_z,
+                       int* info);
+int gps_fitc_train_tall(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* Z0, int m,
+                        const double* theta0, int n_ell, int64_t itr, double lr, double lr_z,
+                        const double* Xt, const double* yt, int64_t nt, int flags,
+                        double* theta_out, double* z_out, double* values, double* thetas,
+                        double* obj, double* mu, double* var, double* sc, int* info,
+                        int* steps_done);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */
 int gps_comm_unique_id(char uid[128]);

@@ -310,6 +310,34 @@ struct BatchFitcParams {
 };
 size_t batch_fitc_lds_bytes(int n, int m, int d);
 
+// batches of tall FITC GPs, one workgroup per problem (kernels_batch_fitc_tall.hip):
+// BatchFitcParams' model and semantics with the n-sized arrays in a per-problem device workspace
+// instead of LDS, so n is bounded by time, not by the CU's 160 KB.  Why 2048: one evaluation is
+// about 10·n·m² FMAs on the one CU a problem owns (≈ 21 MFMA at m = 32, of the order of 0.3 ms at
+// a realistic fraction of a CU's FP64 rate), which is where the launch- and PCIe-bound resident
+// step (≈ 0.5 ms at any n this small) stops losing to it for a single problem; beyond
+// it the resident path's 256 CUs win even for small batches.  That is a flop estimate, not a
+// measurement: tools/fitc_tall_bench.py records the per-step time at n = 128..2048, and measured
+//  the kernel is latency-bound, 1.8 ms a step at n = 2048, m = 20, so one problem
+// alone breaks even near n = 650 and the limit is kept for batches: three problems of n = 2048
+// already beat the sequential loop, and 256 cost what one costs.
+#define GPS_BATCH_FITC_TALL_MAX_N 2048
+constexpr int kBatchFitcTallChunk = 128;  // rows of a pass's LDS chunk: two chunk×(m|1) arrays and
+                                          // the six m×m arrays must fit 160 KB at m = 32 (192 rows
+                                          // would not), and a multiple of every column group's 64
+                                          // lanes keeps the row order independent of the chunking
+struct BatchFitcTallParams {
+  BatchFitcParams b;
+  double* ws;           // [nprob][ws_stride] V, U (n×(m|1) each), then nine n-vectors
+  int64_t ws_stride;    // >= batch_fitc_tall_ws_doubles(n, m)
+};
+size_t batch_fitc_tall_lds_bytes(int n, int m, int d);
+int64_t batch_fitc_tall_ws_doubles(int64_t n, int m);
+// SGD steps one launch may run: a step's cost grows with the chunk count, so kBatchStepsPerLaunch
+// is divided by it (64 up to n = 128, 16 at n = 500, 4 at n = 2048): a function of n alone
+int batch_fitc_tall_steps(int64_t n);
+hipError_t launch_batch_fitc_tall(const BatchFitcTallParams& p, hipStream_t s);
+
 // ------------------------------------------------------------------ launchers
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 hipError_t launch_batch(const BatchParams& p, hipStream_t s);

@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (BATCH_FITC_MAX_M, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
+from ._lib import (BATCH_FITC_MAX_M, BATCH_FITC_TALL_MAX_N, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
                    SCORE_NAMES, f64, ptr)
 
 BATCH_OBJS = OBJ_NAMES[:3]  # nlml, loo_crps, loo_logs
@@ -42,7 +42,7 @@ def _iptr(a):
     return a.ctypes.data_as(_PI)
 
 
-def _problems(X, y):
+def _problems(X, y, max_n=BATCH_MAX_N):
     """(X (B, n, d), y (B, n)) checked against the kernel's limits."""
     try:
         X, y = f64(X), f64(y)
@@ -57,8 +57,8 @@ def _problems(X, y):
         raise ValueError(f"X {X.shape} and y {y.shape} disagree on (B, n)")
     if B < 1:
         raise ValueError("the batch is empty")
-    if not 1 <= n <= BATCH_MAX_N:
-        raise ValueError(f"n = {n}: a batched problem holds 1..{BATCH_MAX_N} training points")
+    if not 1 <= n <= max_n:
+        raise ValueError(f"n = {n}: a batched problem holds 1..{max_n} training points")
     if not 1 <= d <= BATCH_MAX_D:
         raise ValueError(f"d = {d}: a batched problem has 1..{BATCH_MAX_D} input dimensions")
     return np.ascontiguousarray(X), np.ascontiguousarray(y)
@@ -213,11 +213,8 @@ def _inducing(Z, B, d):
     return np.ascontiguousarray(Z), m
 
 
-def fitc_value_and_grad_batch(X, y, Z, theta, objective="loo_crps", ctx=None):
-    """Objective value and analytic gradient of B small FITC GPs at their own (θ, Z) (one
-    gps_fitc_grad_batch call; per problem what GP.value_and_grad(..., Z=Z) returns).  Returns
-    (values (B,), grads (B, 2 + n_ell), grad_Z (B, m, d), objectives {name: (B,)}, info (B,))."""
-    X, y = _problems(X, y)
+def _fitc_value_and_grad(entry, max_n, X, y, Z, theta, objective, ctx):
+    X, y = _problems(X, y, max_n)
     B, n, d = X.shape
     Z, m = _inducing(Z, B, d)
     th, n_ell = _thetas(theta, B, d)
@@ -227,10 +224,18 @@ def fitc_value_and_grad_batch(X, y, Z, theta, objective="loo_crps", ctx=None):
     grad = np.empty((B, 2 + n_ell))
     gz = np.empty((B, m, d))
     info = np.zeros(B, np.int32)
-    ctx.call("gps_fitc_grad_batch", code, B, ptr(X), ptr(y), n, d, ptr(Z), m, ptr(th), n_ell,
+    ctx.call(entry, code, B, ptr(X), ptr(y), n, d, ptr(Z), m, ptr(th), n_ell,
              ptr(obj), ptr(grad), ptr(gz), _iptr(info))
     objs = {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
     return objs[objective], grad, gz, objs, info
+
+
+def fitc_value_and_grad_batch(X, y, Z, theta, objective="loo_crps", ctx=None):
+    """Objective value and analytic gradient of B small FITC GPs at their own (θ, Z) (one
+    gps_fitc_grad_batch call; per problem what GP.value_and_grad(..., Z=Z) returns).  Returns
+    (values (B,), grads (B, 2 + n_ell), grad_Z (B, m, d), objectives {name: (B,)}, info (B,))."""
+    return _fitc_value_and_grad("gps_fitc_grad_batch", BATCH_MAX_N, X, y, Z, theta, objective,
+                                ctx)
 
 
 @dataclass
@@ -240,13 +245,9 @@ class FitcBatchTrainResult(BatchTrainResult):
     Z: np.ndarray = None
 
 
-def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, itr=400, Xt=None,
-                     yt=None, stale_noise=False, ctx=None):
-    """The SGD fit loop of the FITC scripts (`itr` steps θ -= lr·grad, Z -= lr_z·grad_Z,
-    SF:229-233; lr_z defaults to lr) for B small FITC GPs at once on the device, then one forward
-    at the final θ and Z with the test predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score
-    bundle against ``yt`` (B, nt).  ``stale_noise`` as train_batch."""
-    X, y = _problems(X, y)
+def _fitc_train(entry, max_n, X, y, Z0, theta0, objective, lr, lr_z, itr, Xt, yt, stale_noise,
+                ctx):
+    X, y = _problems(X, y, max_n)
     B, n, d = X.shape
     Z0, m = _inducing(Z0, B, d)
     th0, n_ell = _thetas(theta0, B, d)
@@ -265,7 +266,7 @@ def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, 
     var = np.empty((B, nt)) if nt else None
     sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
     info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call("gps_fitc_train_batch", code, B, ptr(X), ptr(y), n, d, ptr(Z0), m, ptr(th0), n_ell,
+    ctx.call(entry, code, B, ptr(X), ptr(y), n, d, ptr(Z0), m, ptr(th0), n_ell,
              itr, lr, lr_z, ptr(Xt), ptr(yt), nt, GPS_BATCH_STALE_NOISE if stale_noise else 0,
              ptr(theta), ptr(Z), ptr(values), ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc),
              _iptr(info), _iptr(steps))
@@ -274,3 +275,31 @@ def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, 
         objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
         scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
         info=info, steps_done=steps, Z=Z)
+
+
+def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, itr=400, Xt=None,
+                     yt=None, stale_noise=False, ctx=None):
+    """The SGD fit loop of the FITC scripts (`itr` steps θ -= lr·grad, Z -= lr_z·grad_Z,
+    SF:229-233; lr_z defaults to lr) for B small FITC GPs at once on the device, then one forward
+    at the final θ and Z with the test predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score
+    bundle against ``yt`` (B, nt).  ``stale_noise`` as train_batch."""
+    return _fitc_train("gps_fitc_train_batch", BATCH_MAX_N, X, y, Z0, theta0, objective, lr, lr_z,
+                       itr, Xt, yt, stale_noise, ctx)
+
+
+def fitc_value_and_grad_tall(X, y, Z, theta, objective="loo_crps", ctx=None):
+    """fitc_value_and_grad_batch for tall problems, 1 <= n <= 2048 (one gps_fitc_grad_tall call,
+    DESIGN §22: one workgroup per problem with the n-sized arrays in a device workspace instead
+    of LDS).  Same arguments, returns, refusals and ``info``; for n <= 128 the small-batch call
+    is the faster route."""
+    return _fitc_value_and_grad("gps_fitc_grad_tall", BATCH_FITC_TALL_MAX_N, X, y, Z, theta,
+                                objective, ctx)
+
+
+def fitc_train_tall(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, itr=400, Xt=None,
+                    yt=None, stale_noise=False, ctx=None):
+    """fitc_train_batch for tall problems, 1 <= n <= 2048 (one gps_fitc_train_tall call): the
+    replicate loops of "KIN40K-COMPARE-ALL-FITC-20" (n = 500, d = 8, m = 20) for B problems at
+    once.  Same arguments, refusals and FitcBatchTrainResult."""
+    return _fitc_train("gps_fitc_train_tall", BATCH_FITC_TALL_MAX_N, X, y, Z0, theta0, objective,
+                       lr, lr_z, itr, Xt, yt, stale_noise, ctx)
