@@ -59,8 +59,9 @@ enum {
  * gps_gemm_schedule added; 900: the batched small GPs, gps_full_grad_batch / gps_full_train_batch
  * added).  gps_fitc_grad_batch / gps_fitc_train_batch joined at 900 without a bump:
  * they are purely additive, no existing entry point or array changed; so did gps_potrf_diag
- *  and gps_fitc_grad_tall / gps_fitc_train_tall.  The binding refuses a
- * mismatch at load. */
+ * (DESIGN §21), gps_fitc_grad_tall / gps_fitc_train_tall and the gradient-layer
+ * diagnostics gps_grad_terms_diag / gps_grad_contract_diag / gps_fitc_contract_diag.
+ * The binding refuses a mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
 /* The SHA-256 (hex) of the sources the library was built from (csrc/, this header; computed by
@@ -246,6 +247,43 @@ enum { GPS_POTRF_PLAN_NPAD = 0, GPS_POTRF_PLAN_LEAVES = 1, GPS_POTRF_PLAN_DAGS =
        GPS_POTRF_PLAN_REPLAYED = 6, GPS_N_POTRF_PLAN = 8 };
 int gps_potrf_diag(gps_ctx* ctx, int64_t n, const double* A, int64_t lda, double* L, double* Linv,
                    double* logdiag, int32_t* info, int32_t* plan);
+
+/* Diagnostics: the gradient layer's kernels one launch at a time on host arrays
+ * (tests/test_gpu_grad_terms.py).  Each call judges its arguments before anything
+ * touches the device (-1 with the reason in gps_last_error), uploads, calls the production
+ * launcher, and copies the outputs back; what a kernel must write, and what it must not read, is
+ * NaN on the device beforehand.
+ *
+ * gps_grad_terms_diag, the per-point terms.  in / out are arrays of pointers (in: 8, out: 6
+ * slots; unused slots are not read), every vector n long on input and n_pad long on output:
+ *   which 0  loo_grad_terms   in {y, alpha, dinv}; obj LOO_CRPS / LOO_LOGS; out {u, ct}
+ *   which 1  fitc_grad_terms  in {y, lam, r, g}; obj NLML / LOO_*; scal = n_total;
+ *                             out {alpha, dinv, v, ulam, h, hl2}
+ *   which 2  fold_terms       in {y, r, c}; n = b = n_pad; out {gm or NULL, gc, value[1]}
+ *                             (gc may be NULL with gm)
+ *   which 3  fitc_grad_mdiag  in {KN or NULL, K, lam, r, dinv, alpha, v, h or NULL}, KN and K
+ *                             [n][m_pad] (m_pad even; K may be NULL with KN); scal = a;
+ *                             out {mdiag, s1, s2, s3}
+ * m_pad is read by which 3 only. */
+int gps_grad_terms_diag(gps_ctx* ctx, int which, int obj, int64_t n, int64_t n_pad, int64_t m_pad,
+                        double scal, const double* const* in, double* const* out);
+/* launch_grad_contract on X [n][d], Ainv / Mx [n][ld] (either NULL with its coefficient a[0] /
+ * a[3] zero; v NULL with a[2] zero — the kernel then gets a buffer of NaN, not a null pointer),
+ * a[4] = {a0, a1, a2, a3}.  out: ceil(d/16) × 18 doubles as the launcher writes them —
+ * per pass [Σ w·m·K, Σ_{i=j} m, Σ w·m·K·Δ_k² for the pass's 16 dimensions]. */
+int gps_grad_contract_diag(gps_ctx* ctx, int64_t n, int d, const double* X, const double* inv_ell,
+                           double sf2, const double* Ainv, const double* Mx, int64_t ld,
+                           const double* alpha, const double* v, const double* a, double* out);
+/* launch_fitc_grad_contract on xr [nr][d], xc [nc][d], nt <= 4 matrix terms R[t] [nr][ldr[t]] with
+ * coef[t] and row scales rs[t] (rs, or any rs[t], may be NULL), two rank-one terms pc[q]·pv[q]·
+ * qv[q]ᵀ (pc[q] = 0: off, the vectors are not read).  out: ceil(d/16) × 17 doubles
+ * [Σ G·K, Σ G·K·Δ_k²], zout [nc][d] = Σ_i G·K·Δ_k.  On the device every array has a NaN tail past
+ * its real rows and columns. */
+int gps_fitc_contract_diag(gps_ctx* ctx, int64_t nr, int64_t nc, int64_t nc_pad, int d,
+                           const double* xr, const double* xc, const double* inv_ell, double sf2,
+                           int nt, const double* const* R, const int64_t* ldr, const double* coef,
+                           const double* const* rs, const double* pc, const double* const* pv,
+                           const double* const* qv, double* out, double* zout);
 
 /* on: 0 off, 1 per-kernel-class tags, 2 GEMM tags also carry layout/shape/tri/split-K/lda */
 int gps_prof_enable(gps_ctx* ctx, int on);

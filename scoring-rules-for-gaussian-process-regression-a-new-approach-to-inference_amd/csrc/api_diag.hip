@@ -2,7 +2,9 @@
 // internal launch on host arrays, so the tests can drive every kernel variant alone and compare
 // it exactly (tests/test_gpu_gemm_modes.py); and of the factorisation
 // (gps_potrf_diag): gps_potrf's own path with every buffer it wrote copied back whole
-// (tests/test_gpu_factor.py).  Nothing here is on a production path.
+// (tests/test_gpu_factor.py); and of the gradient layer (gps_grad_terms_diag,
+// gps_grad_contract_diag, gps_fitc_contract_diag): one production launch_* call each on host
+// arrays (tests/test_gpu_grad_terms.py).  Nothing here is on a production path.
 #include "api_internal.h"
 
 // (the binding's ctypes structure is checked against the same size: tests/test_gemm_diag_args.py)
@@ -235,6 +237,248 @@ int gps_potrf_diag(gps_ctx* ctx, int64_t n, const double* A, int64_t lda, double
   for (int i = 0; i < GPS_N_POTRF_PLAN; ++i) plan[i] = v[i];
   return 0;
 }
+
+// ---- the gradient layer's launches on host arrays (tests/test_gpu_grad_terms.py).
+// Each call judges its arguments, binds, carves device space from the compat scratch (t0: inputs,
+// t1 / t2: matrices, gslab / gout: the contractions' slabs and outputs), fills what the kernel
+// must write or must not read with NaN (bytes of 0xFF), calls the production launch_* and copies
+// back.  No context member is added.
+#define DIAG_REQ(cond, msg) \
+  do {                      \
+    if (!(cond)) return fail(ctx, -1, std::string(kWho) + msg); \
+  } while (0)
+
+int gps_grad_terms_diag(gps_ctx* ctx, int which, int obj, int64_t n, int64_t n_pad, int64_t m_pad,
+                        double scal, const double* const* in, double* const* out) {
+  static const char kWho[] = "gps_grad_terms_diag: ";
+  DIAG_REQ(in && out, "NULL argument");
+  DIAG_REQ(which >= 0 && which <= 3, "which must be 0..3");
+  DIAG_REQ(n >= 1 && n <= (1 << 20), "n must be in 1..2^20");
+  DIAG_REQ(std::isfinite(scal), "the scalar must be finite");
+  // per call: inputs (count, each n long unless a matrix), outputs (count, each n_pad long)
+  int n_in = 0, n_out = 0;
+  int64_t in_len[8] = {0}, out_len[6] = {0};
+  bool in_opt[8] = {false}, out_opt[6] = {false};
+  if (which == 2) {
+    DIAG_REQ(n_pad == n, "the fold terms have no padding: n_pad must equal n");
+    n_in = 3; n_out = 3;
+    out_len[0] = out_len[1] = n; out_len[2] = 1;
+    out_opt[0] = out_opt[1] = true;
+    DIAG_REQ(!out[0] || out[1], "gm without gc");
+  } else {
+    DIAG_REQ(n_pad >= n && n_pad <= (1 << 20), "n_pad must be in n..2^20");
+    if (which == 0) {
+      DIAG_REQ(obj == GPS_OBJ_LOO_CRPS || obj == GPS_OBJ_LOO_LOGS, "objective must be LOO-CRPS or LOO-LogS");
+      n_in = 3; n_out = 2;
+    } else if (which == 1) {
+      DIAG_REQ(obj == GPS_OBJ_NLML || obj == GPS_OBJ_LOO_CRPS || obj == GPS_OBJ_LOO_LOGS,
+               "objective must be NLML, LOO-CRPS or LOO-LogS");
+      DIAG_REQ(scal > 0.0, "n_total must be positive");
+      n_in = 4; n_out = 6;
+    } else {
+      DIAG_REQ(m_pad >= 2 && m_pad % 2 == 0 && m_pad <= 4096, "m_pad must be even, in 2..4096");
+      DIAG_REQ(n * m_pad <= ((int64_t)1 << 24), "n*m_pad <= 2^24");
+      n_in = 8; n_out = 4;
+      in_opt[0] = in_opt[7] = true;
+      DIAG_REQ(!in[0] || in[1], "KN without K");
+      in_opt[1] = !in[0];
+    }
+    for (int q = 0; q < n_out; ++q) out_len[q] = n_pad;
+  }
+  for (int q = 0; q < n_in; ++q) {
+    in_len[q] = which == 3 && q < 2 ? n * m_pad : n;
+    DIAG_REQ(in[q] || in_opt[q], "NULL input array");
+  }
+  for (int q = 0; q < n_out; ++q) DIAG_REQ(out[q] || out_opt[q], "NULL output array");
+  if (int rc = bind(ctx)) return rc;
+  hipStream_t s = ctx->stream;
+  auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
+  int64_t tot_in = 2, tot_out = 2;
+  for (int q = 0; q < n_in; ++q) tot_in += even(in_len[q]);
+  for (int q = 0; q < n_out; ++q) tot_out += even(out_len[q]);
+  HIPCHK(ensure(ctx, ctx->t0, (size_t)tot_in * 8));
+  HIPCHK(ensure(ctx, ctx->t1, (size_t)tot_out * 8));
+  HIPCHK(hipMemsetAsync(ctx->t1.d(), 0xFF, (size_t)tot_out * 8, s));
+  const double* di[8] = {nullptr};
+  double* dout[6] = {nullptr};
+  double* w = ctx->t0.d();
+  for (int q = 0; q < n_in; ++q) {
+    if (in[q]) {
+      HIPCHK(hipMemcpyAsync(w, in[q], (size_t)in_len[q] * 8, hipMemcpyHostToDevice, s));
+      di[q] = w;
+    }
+    w += even(in_len[q]);
+  }
+  w = ctx->t1.d();
+  for (int q = 0; q < n_out; ++q) {
+    if (out[q]) dout[q] = w;
+    w += even(out_len[q]);
+  }
+  const int ni = (int)n, np = (int)n_pad;
+  switch (which) {
+    case 0:
+      HIPCHK(launch_loo_grad_terms(di[0], di[1], di[2], ni, np, obj, dout[0], dout[1], s));
+      break;
+    case 1:
+      HIPCHK(launch_fitc_grad_terms(di[0], di[1], di[2], di[3], ni, np, obj, scal, dout[0], dout[1],
+                                    dout[2], dout[3], dout[4], dout[5], s));
+      break;
+    case 2:
+      HIPCHK(launch_fold_terms(di[0], di[1], di[2], ni, dout[0], dout[1], dout[2], s));
+      break;
+    default:
+      HIPCHK(launch_fitc_grad_mdiag(di[0], m_pad, di[1], m_pad, (int)m_pad, di[2], di[3], di[4], di[5],
+                                    di[6], di[7], scal, ni, np, dout[0], dout[1], dout[2], dout[3], s));
+      break;
+  }
+  for (int q = 0; q < n_out; ++q)
+    if (out[q])
+      HIPCHK(hipMemcpyAsync(out[q], dout[q], (size_t)out_len[q] * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gps_grad_contract_diag(gps_ctx* ctx, int64_t n, int d, const double* X, const double* inv_ell,
+                           double sf2, const double* Ainv, const double* Mx, int64_t ld,
+                           const double* alpha, const double* v, const double* a, double* out) {
+  static const char kWho[] = "gps_grad_contract_diag: ";
+  DIAG_REQ(X && inv_ell && alpha && a && out, "NULL argument");
+  DIAG_REQ(d >= 1 && d <= GPS_MAX_D, "d must be in 1..64");
+  DIAG_REQ(n >= 1 && n <= 8192, "n must be in 1..8192");
+  DIAG_REQ(ld >= n && ld <= 16384, "ld must be in n..16384");
+  DIAG_REQ(std::isfinite(sf2) && std::isfinite(a[0]) && std::isfinite(a[1]) &&
+               std::isfinite(a[2]) && std::isfinite(a[3]),
+           "sf2 and the coefficients must be finite");
+  DIAG_REQ(Ainv || a[0] == 0.0, "a0 != 0 needs Ainv");
+  DIAG_REQ(v || a[2] == 0.0, "a2 != 0 needs v");
+  DIAG_REQ(Mx || a[3] == 0.0, "a3 != 0 needs Mx");
+  if (int rc = bind(ctx)) return rc;
+  hipStream_t s = ctx->stream;
+  auto even = [](int64_t x) { return (x + 1) & ~(int64_t)1; };
+  // every array reaches to the end of the last 64-row tile, NaN past its real rows; an absent
+  // operand is a live buffer of NaN (the production call always passes a pointer)
+  const int64_t nt64 = (n + 63) / 64 * 64;
+  const int64_t nx = even(nt64 * d), nv = even(nt64), nm = nt64 * ld;
+  const int passes = grad_contract_passes(d);
+  const int64_t slab = grad_contract_slab_doubles((int)n, d);
+  HIPCHK(ensure(ctx, ctx->t0, (size_t)(nx + 2 * nv) * 8));
+  HIPCHK(ensure(ctx, ctx->t1, (size_t)nm * 8));
+  HIPCHK(ensure(ctx, ctx->t2, (size_t)nm * 8));
+  HIPCHK(ensure(ctx, ctx->gslab, (size_t)slab * 8));
+  HIPCHK(ensure(ctx, ctx->gout, (size_t)passes * 18 * 8));
+  double* dX = ctx->t0.d();
+  double* dal = dX + nx;
+  double* dv = dal + nv;
+  HIPCHK(hipMemsetAsync(ctx->t0.d(), 0xFF, (size_t)(nx + 2 * nv) * 8, s));
+  HIPCHK(hipMemsetAsync(ctx->t1.d(), 0xFF, (size_t)nm * 8, s));
+  HIPCHK(hipMemsetAsync(ctx->t2.d(), 0xFF, (size_t)nm * 8, s));
+  auto put = [&](double* dst, const double* src, int64_t cnt) {
+    return src ? hipMemcpyAsync(dst, src, (size_t)cnt * 8, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  HIPCHK(put(dX, X, n * d));
+  HIPCHK(put(dal, alpha, n));
+  HIPCHK(put(dv, v, n));
+  HIPCHK(put(ctx->t1.d(), Ainv, n * ld));
+  HIPCHK(put(ctx->t2.d(), Mx, n * ld));
+  HIPCHK(hipMemsetAsync(ctx->gslab.d(), 0xFF, (size_t)slab * 8, s));
+  HIPCHK(hipMemsetAsync(ctx->gout.d(), 0xFF, (size_t)passes * 18 * 8, s));
+  GradParams g{};
+  g.x = dX; g.n = (int)n; g.d = d; g.sf2 = sf2;
+  for (int k = 0; k < d; ++k) g.inv_ell[k] = inv_ell[k];
+  g.Ainv = ctx->t1.d(); g.Mx = ctx->t2.d(); g.ldm = ld;
+  g.alpha = dal; g.v = dv;
+  g.a0 = a[0]; g.a1 = a[1]; g.a2 = a[2]; g.a3 = a[3];
+  g.slab = ctx->gslab.d();
+  HIPCHK(launch_grad_contract(g, ctx->gout.d(), s));
+  HIPCHK(hipMemcpyAsync(out, ctx->gout.d(), (size_t)passes * 18 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int gps_fitc_contract_diag(gps_ctx* ctx, int64_t nr, int64_t nc, int64_t nc_pad, int d,
+                           const double* xr, const double* xc, const double* inv_ell, double sf2,
+                           int nt, const double* const* R, const int64_t* ldr, const double* coef,
+                           const double* const* rs, const double* pc, const double* const* pv,
+                           const double* const* qv, double* out, double* zout) {
+  static const char kWho[] = "gps_fitc_contract_diag: ";
+  DIAG_REQ(xr && xc && inv_ell && pc && out && zout, "NULL argument");
+  DIAG_REQ(d >= 1 && d <= GPS_MAX_D, "d must be in 1..64");
+  DIAG_REQ(nr >= 1 && nr <= (1 << 20), "nr must be in 1..2^20");
+  DIAG_REQ(nc >= 1 && nc <= 16384, "nc must be in 1..16384");
+  DIAG_REQ(nc_pad >= nc && nc_pad <= nc + 128, "nc_pad must be in nc..nc+128");
+  DIAG_REQ(nt >= 0 && nt <= 4, "nt must be in 0..4");
+  DIAG_REQ(nt == 0 || (R && ldr && coef), "matrix terms need R, ldr and coef");
+  DIAG_REQ(std::isfinite(sf2) && std::isfinite(pc[0]) && std::isfinite(pc[1]),
+           "sf2 and the coefficients must be finite");
+  int64_t rtot = 0;
+  for (int t = 0; t < nt; ++t) {
+    DIAG_REQ(R[t], "NULL matrix term");
+    DIAG_REQ(ldr[t] >= nc && ldr[t] <= 32768, "ldr must be in nc..32768");
+    DIAG_REQ(std::isfinite(coef[t]), "sf2 and the coefficients must be finite");
+    rtot += (nr + 16) * ldr[t];
+  }
+  DIAG_REQ(rtot <= ((int64_t)1 << 26), "the matrix terms exceed 2^26 doubles");
+  for (int q = 0; q < 2; ++q)
+    DIAG_REQ(pc[q] == 0.0 || (pv && qv && pv[q] && qv[q]), "a rank-one term needs pv and qv");
+  if (int rc = bind(ctx)) return rc;
+  hipStream_t s = ctx->stream;
+  // every array gets a tail past its real extent (16 rows: one batch of the row loop; 64 columns:
+  // one column block), and everything not uploaded is NaN
+  const int64_t nrt = nr + 16, nct = nc_pad + 64;
+  const int64_t vec = nrt * d + nct * d + 6 * nrt + 2 * nct;
+  const int passes = fitc_contract_passes(d);
+  const int64_t slab = fitc_contract_slab_doubles((int)nr, (int)nc_pad, d);
+  const int64_t nout = passes * 17 + nc * d;
+  HIPCHK(ensure(ctx, ctx->t0, (size_t)vec * 8));
+  HIPCHK(ensure(ctx, ctx->t1, (size_t)std::max<int64_t>(rtot, 2) * 8));
+  HIPCHK(ensure(ctx, ctx->gslab, (size_t)slab * 8));
+  HIPCHK(ensure(ctx, ctx->gout, (size_t)nout * 8));
+  HIPCHK(hipMemsetAsync(ctx->t0.d(), 0xFF, (size_t)vec * 8, s));
+  HIPCHK(hipMemsetAsync(ctx->t1.d(), 0xFF, (size_t)std::max<int64_t>(rtot, 2) * 8, s));
+  HIPCHK(hipMemsetAsync(ctx->gslab.d(), 0xFF, (size_t)slab * 8, s));
+  HIPCHK(hipMemsetAsync(ctx->gout.d(), 0xFF, (size_t)nout * 8, s));
+  auto up = [&](double* dst, const double* src, int64_t cnt) {
+    return hipMemcpyAsync(dst, src, (size_t)cnt * 8, hipMemcpyHostToDevice, s);
+  };
+  FitcContractParams p{};
+  double* w = ctx->t0.d();
+  HIPCHK(up(w, xr, nr * d)); p.xr = w; w += nrt * d;
+  HIPCHK(up(w, xc, nc * d)); p.xc = w; w += nct * d;
+  p.nr = (int)nr; p.nc = (int)nc; p.nc_pad = (int)nc_pad; p.d = d; p.sf2 = sf2;
+  for (int k = 0; k < d; ++k) p.inv_ell[k] = inv_ell[k];
+  p.nt = nt;
+  double* m = ctx->t1.d();
+  for (int t = 0; t < 4; ++t) {
+    if (t < nt) {
+      HIPCHK(up(m, R[t], nr * ldr[t]));
+      p.R[t] = m; p.ldr[t] = ldr[t]; p.coef[t] = coef[t];
+      m += nrt * ldr[t];
+      if (rs && rs[t]) {
+        HIPCHK(up(w, rs[t], nr));
+        p.rs[t] = w;
+      }
+    }
+    w += nrt;
+  }
+  for (int q = 0; q < 2; ++q) {
+    p.pc[q] = pc[q];
+    // a rank-one term that is off still gets live (NaN) vectors, as the production call has
+    p.pv[q] = w;
+    if (pc[q] != 0.0) HIPCHK(up(w, pv[q], nr));
+    w += nrt;
+    p.qv[q] = w;
+    if (pc[q] != 0.0) HIPCHK(up(w, qv[q], nc));
+    w += nct;
+  }
+  p.slab = ctx->gslab.d();
+  HIPCHK(launch_fitc_grad_contract(p, ctx->gout.d(), ctx->gout.d() + passes * 17, s));
+  HIPCHK(hipMemcpyAsync(out, ctx->gout.d(), (size_t)passes * 17 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(zout, ctx->gout.d() + passes * 17, (size_t)nc * d * 8,
+                        hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+#undef DIAG_REQ
 
 int64_t gps_gemm_schedule(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int slots,
                           int32_t* plan, int32_t* items, int64_t cap) {

@@ -187,8 +187,8 @@ __device__ __forceinline__ void gradient(const Lds& s, int n, int d, int objecti
   double* A = s.A;
   const bool loo = objective != GPS_OBJ_NLML;
   if (loo && t < n) {  // score_derivs of the MEAN score, then u and c̃ (kernels_grad.hip)
-    const double dd = s.dinv[t], a = s.alpha[t], yy = s.y[t];
-    const double m = yy - a / dd, c = 1.0 / dd, r = yy - m;
+    const double dd = s.dinv[t], a = s.alpha[t];
+    const double c = 1.0 / dd, r = a / dd;  // y − μ_loo = α/d (kernels_grad.hip)
     double gm, gc;
     if (objective == GPS_OBJ_LOO_CRPS) {
       const double sd = sqrt(c), z = r / sd;

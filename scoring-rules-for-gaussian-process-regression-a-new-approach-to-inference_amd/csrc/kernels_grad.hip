@@ -31,7 +31,8 @@ __global__ __launch_bounds__(256) void loo_grad_terms_kernel(const double* __res
     return;
   }
   const double d = dinv[i], a = alpha[i];
-  const double m = y[i] - a / d, c = 1.0 / d, r = y[i] - m;
+  // y − μ_loo is α/d itself: forming it as y − (y − α/d) loses u·|y| absolutely
+  const double c = 1.0 / d, r = a / d;
   double gm, gc;
   if (obj == GPS_OBJ_LOO_CRPS) {  // KF:60-68: ∂/∂m = 1 − 2Φ(z), ∂/∂c = (2φ(z) − 1/√π)/(2σ)
     const double s = sqrt(c), z = r / s;

@@ -47,6 +47,8 @@ _c_int, _c_i64, _c_dbl, _c_vp, _c_cp = (ctypes.c_int, ctypes.c_int64, ctypes.c_d
 _P = ctypes.POINTER(ctypes.c_double)
 
 _PI = ctypes.POINTER(ctypes.c_int32)
+_PI64 = ctypes.POINTER(ctypes.c_int64)
+_PP = ctypes.POINTER(_P)  # an array of float64 pointers (the gradient diagnostics)
 
 
 class GemmDesc(ctypes.Structure):
@@ -88,6 +90,12 @@ SIGNATURES = {
     "gps_gemm_diag": (_c_int, [_c_vp, ctypes.POINTER(GemmDesc), _P, _P, _P, _P, _P, _PI, _P, _P,
                                _PI]),
     "gps_potrf_diag": (_c_int, [_c_vp, _c_i64, _P, _c_i64, _P, _P, _P, _PI, _PI]),
+    "gps_grad_terms_diag": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_dbl, _PP,
+                                     _PP]),
+    "gps_grad_contract_diag": (_c_int, [_c_vp, _c_i64, _c_int, _P, _P, _c_dbl, _P, _P, _c_i64, _P,
+                                        _P, _P, _P]),
+    "gps_fitc_contract_diag": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P, _P, _P, _c_dbl,
+                                        _c_int, _PP, _PI64, _P, _PP, _P, _PP, _PP, _P, _P]),
     "gps_prof_enable": (_c_int, [_c_vp, _c_int]),
     "gps_prof_collect": (_c_int, [_c_vp, _c_cp, _c_i64]),
     "gps_phase_enable": (_c_int, [_c_vp, _c_int]),
@@ -251,6 +259,42 @@ def f64(a, ndim=None):
     return a
 
 
+def _ptr_array(arrays, slots):
+    """A C array of float64 pointers, NULL for None and for the unused slots."""
+    a = (_P * slots)()
+    for i, v in enumerate(arrays):
+        if v is not None:
+            a[i] = v.ctypes.data_as(_P)
+    return a
+
+
+# The gradient diagnostics' raw calls: the handle may be None (the argument checks come before the
+# context is looked at, tests/test_grad_terms_host.py); they return the status.
+def grad_terms_diag_raw(h, which, obj, n, n_pad, ins, outs, scal=1.0, m_pad=0):
+    pi = None if ins is None else _ptr_array(ins, 8)
+    po = None if outs is None else _ptr_array(outs, 6)
+    return load().gps_grad_terms_diag(h, which, obj, n, n_pad, m_pad, scal, pi, po)
+
+
+def grad_contract_diag_raw(h, n, d, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a, out):
+    return load().gps_grad_contract_diag(h, n, d, ptr(X), ptr(inv_ell), sf2, ptr(Ainv), ptr(Mx), ld,
+                                         ptr(alpha), ptr(v), ptr(a), ptr(out))
+
+
+def fitc_contract_diag_raw(h, nr, nc, nc_pad, d, xr, xc, inv_ell, sf2, R, coef, rs, pc, pv, qv,
+                           out, zout, nt=None, ldr=None):
+    nt = len(R) if nt is None else nt
+    ldr = np.array([m.shape[1] for m in R] if ldr is None else ldr, np.int64)
+    coef = np.ascontiguousarray(coef, np.float64)
+    pc = None if pc is None else np.ascontiguousarray(pc, np.float64)
+    return load().gps_fitc_contract_diag(
+        h, nr, nc, nc_pad, d, ptr(xr), ptr(xc), ptr(inv_ell), sf2, nt,
+        _ptr_array(R, 4) if len(R) else None, ldr.ctypes.data_as(_PI64) if len(ldr) else None,
+        ptr(coef) if len(coef) else None, None if rs is None else _ptr_array(rs, 4), ptr(pc),
+        None if pv is None else _ptr_array(pv, 2), None if qv is None else _ptr_array(qv, 2),
+        ptr(out), ptr(zout))
+
+
 class Context:
     """One device + one HIP stream + the device-resident buffers of the hot path."""
 
@@ -389,6 +433,34 @@ class Context:
                                            info.ctypes.data_as(_PI), plan.ctypes.data_as(_PI)),
                    "gps_potrf_diag")
         return L, Li, ld, int(info[0]), dict(zip(POTRF_PLAN_NAMES, (int(v) for v in plan)))
+
+    def grad_terms_diag(self, which, obj, n, n_pad, ins, outs, scal=1.0, m_pad=0):
+        """One per-point gradient-term launch on host arrays (gps_grad_terms_diag; diagnostics):
+        ins / outs are the arrays in the header's order, None where one is absent; outs are
+        written in place."""
+        self.check(grad_terms_diag_raw(self.h, which, obj, n, n_pad, ins, outs, scal, m_pad),
+                   "gps_grad_terms_diag")
+
+    def grad_contract_diag(self, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a):
+        """launch_grad_contract on host arrays (gps_grad_contract_diag; diagnostics): the
+        passes x 18 block as the launcher writes it."""
+        n, d = X.shape
+        out = np.full(((d + 15) // 16, 18), np.nan)
+        self.check(grad_contract_diag_raw(self.h, n, d, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a,
+                                          out), "gps_grad_contract_diag")
+        return out
+
+    def fitc_contract_diag(self, xr, xc, nc_pad, inv_ell, sf2, R=(), coef=(), rs=None,
+                           pc=(0.0, 0.0), pv=(None, None), qv=(None, None)):
+        """launch_fitc_grad_contract on host arrays (gps_fitc_contract_diag; diagnostics):
+        (out [passes][17], zout [nc][d]).  R: up to four [nr][ldr] matrices (ldr their row
+        length), rs: None or one entry (an array or None) per matrix."""
+        (nr, d), nc = xr.shape, xc.shape[0]
+        out = np.full(((d + 15) // 16, 17), np.nan)
+        zout = np.full((nc, d), np.nan)
+        self.check(fitc_contract_diag_raw(self.h, nr, nc, nc_pad, d, xr, xc, inv_ell, sf2, R, coef,
+                                          rs, pc, pv, qv, out, zout), "gps_fitc_contract_diag")
+        return out, zout
 
     def comm_info(self):
         """(nranks, rank, kind) of the context's communicator as the library sees it: RCCL's own
