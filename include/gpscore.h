@@ -59,8 +59,9 @@ enum {
  * gps_gemm_schedule added; 900: the batched small GPs, gps_full_grad_batch / gps_full_train_batch
  * added).  gps_fitc_grad_batch / gps_fitc_train_batch joined at 900 without a bump:
  * they are purely additive, no existing entry point or array changed; so did gps_potrf_diag
- * (DESIGN §21), gps_fitc_grad_tall / gps_fitc_train_tall and the gradient-layer
- * diagnostics gps_grad_terms_diag / gps_grad_contract_diag / gps_fitc_contract_diag.
+ * (DESIGN §21), gps_fitc_grad_tall / gps_fitc_train_tall, the gradient-layer
+ * diagnostics gps_grad_terms_diag / gps_grad_contract_diag / gps_fitc_contract_diag
+ * and gps_full_grad_tall / gps_full_train_tall.
  * The binding refuses a mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -569,6 +570,27 @@ int gps_fitc_train_tall(gps_ctx* ctx, int objective, int64_t nprob, const double
                         double* theta_out, double* z_out, double* values, double* thetas,
                         double* obj, double* mu, double* var, double* sc, int* info,
                         int* steps_done);
+
+/* ---- batches of full GPs of up to 512 rows ---------------------------
+ * gps_full_grad_batch / gps_full_train_batch for 1 <= n <= 512 training
+ * points: the same argument lists, model (d <= 16, n_ell = 1 or d, GPS_ARD or GPS_RBF; NLML,
+ * LOO-CRPS, LOO-LogS), outputs (which may be NULL included), GPS_BATCH_STALE_NOISE, info codes,
+ * failure semantics and bitwise independence of nprob, position and launch split — the replicate
+ * loop of "kin40k-FULL-compare.py" (n = 500, d = 8; LOO-CRPS 400, NLML 400, LOO-LogS 500 steps).
+ * One workgroup per problem as there; the n×n arrays sit in a per-problem device workspace of the
+ * call's own (two np×np arrays, np = 64·ceil(n/64)) instead of LDS, and the O(n³) work runs tile by
+ * tile on the FP64 matrix instruction; a launch runs min(64, max(1, 1024 / ceil(n/64)³)) steps.
+ * They agree with the small-batch calls and the resident path within rounding, never bitwise; for
+ * n <= 128 the small-batch calls are the faster route.  A batch whose inputs, outputs or workspace
+ * (nprob·2np² doubles) exceed 8 GiB is refused. */
+int gps_full_grad_tall(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                       const double* y, int64_t n, int d, const double* theta, int n_ell,
+                       double* obj, double* grad, int* info);
+int gps_full_train_tall(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* theta0, int n_ell,
+                        int64_t itr, double lr, const double* Xt, const double* yt, int64_t nt,
+                        int flags, double* theta_out, double* values, double* thetas, double* obj,
+                        double* mu, double* var, double* sc, int* info, int* steps_done);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */
 int gps_comm_unique_id(char uid[128]);

@@ -338,6 +338,27 @@ int64_t batch_fitc_tall_ws_doubles(int64_t n, int m);
 int batch_fitc_tall_steps(int64_t n);
 hipError_t launch_batch_fitc_tall(const BatchFitcTallParams& p, hipStream_t s);
 
+// batches of full GPs of up to 512 rows, one workgroup per problem (kernels_batch_full_tall.hip,
+// DESIGN §24): BatchParams' model and semantics with the n×n arrays in a per-problem device
+// workspace instead of LDS and the O(n³) work on the FP64 matrix instruction, tile by tile.  Why
+// 512: a LOO step is about 630 tile products (1.7·10⁸ FMAs) at n = 512, an arithmetic floor of
+// about 1.1 ms on the one CU a problem owns; it grows with n³, and beyond this the resident path's
+// 256 CUs are the better home for all but very large batches.
+#define GPS_BATCH_FULL_TALL_MAX_N 512
+constexpr int kBatchFullTallTile = 64;  // tile edge T: n is padded to a multiple inside the workspace
+struct BatchFullTallParams {
+  BatchParams b;
+  double* ws;           // [nprob][ws_stride]: A / L / P, then X = L⁻¹ (np×np each); 32-byte aligned
+  int64_t ws_stride;    // >= batch_full_tall_ws_doubles(n), a multiple of 4
+};
+size_t batch_full_tall_lds_bytes(int n);
+int64_t batch_full_tall_ws_doubles(int64_t n);
+// SGD steps one launch may run: a step's cost grows with the cube of the block count nb =
+// ceil(n / 64), so it is min(64, max(1, 1024 / nb³)) (64 up to n = 128, 16 at n = 256, 2 at n =
+// 500): a function of n alone
+int batch_full_tall_steps(int64_t n);
+hipError_t launch_batch_full_tall(const BatchFullTallParams& p, hipStream_t s);
+
 // ------------------------------------------------------------------ launchers
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 hipError_t launch_batch(const BatchParams& p, hipStream_t s);

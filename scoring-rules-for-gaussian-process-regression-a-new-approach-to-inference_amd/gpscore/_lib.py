@@ -40,6 +40,7 @@ GPS_BATCH_STALE_NOISE = 1
 BATCH_MAX_N, BATCH_MAX_D = 128, 16  # GPS_SURFACE_MAX_N, GPS_BATCH_MAX_D
 BATCH_FITC_MAX_M = 32  # GPS_BATCH_FITC_MAX_M
 BATCH_FITC_TALL_MAX_N = 2048  # GPS_BATCH_FITC_TALL_MAX_N
+BATCH_FULL_TALL_MAX_N = 512  # GPS_BATCH_FULL_TALL_MAX_N
 SCORE_NAMES = ("test_crps", "test_logs", "test_msll", "test_smse", "test_mse", "test_cover")
 
 _c_int, _c_i64, _c_dbl, _c_vp, _c_cp = (ctypes.c_int, ctypes.c_int64, ctypes.c_double,
@@ -149,6 +150,11 @@ SIGNATURES = {
     "gps_fitc_train_tall": (_c_int, [_c_vp, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P, _c_int, _P,
                                      _c_int, _c_i64, _c_dbl, _c_dbl, _P, _P, _c_i64, _c_int, _P,
                                      _P, _P, _P, _P, _P, _P, _P, _PI, _PI]),
+    "gps_full_grad_tall": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P,
+                                    _c_int, _P, _P, _PI]),
+    "gps_full_train_tall": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P,
+                                     _c_int, _c_i64, _c_dbl, _P, _P, _c_i64, _c_int, _P, _P, _P,
+                                     _P, _P, _P, _P, _PI, _PI]),
     "gps_comm_unique_id": (_c_int, [_c_cp]),
     "gps_comm_init": (_c_int, [_c_vp, _c_int, _c_int, _c_cp]),
     "gps_comm_init_local": (_c_int, [_c_vp, _c_int, _c_int, ctypes.c_longlong]),

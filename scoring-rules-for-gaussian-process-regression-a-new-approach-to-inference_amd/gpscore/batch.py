@@ -1,11 +1,12 @@
 """Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
-(DESIGN §19, §20).
+(DESIGN §19, §20), and their siblings for taller problems (§22, §24).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
     vals, grads, gZ, objs, info = gpscore.fitc_value_and_grad_batch(X, y, Z, theta, "loo_crps")
     res = gpscore.fitc_train_batch(X, y, Z0, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, lr_z=1.0,
                                    itr=1000, Xt=Xt, yt=yt)
+    res = gpscore.train_tall(X, y, theta0, "loo_crps", lr=1.0, itr=400, Xt=Xt, yt=yt)  # n <= 512
 
 The replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120, three SGD
 fits each: SD:192-231, 277-301, 372-396) and contour-plot.R's n = 20 problems are many tiny,
@@ -31,7 +32,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (BATCH_FITC_MAX_M, BATCH_FITC_TALL_MAX_N, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
+from ._lib import (BATCH_FITC_MAX_M, BATCH_FITC_TALL_MAX_N, BATCH_FULL_TALL_MAX_N, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
                    SCORE_NAMES, f64, ptr)
 
 BATCH_OBJS = OBJ_NAMES[:3]  # nlml, loo_crps, loo_logs
@@ -94,11 +95,8 @@ def _objective(objective):
     return OBJ_NAMES.index(objective)
 
 
-def value_and_grad_batch(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
-    """Objective value and analytic gradient of B small full GPs at their own θ (one
-    gps_full_grad_batch call; per problem what GP.value_and_grad returns).  Returns
-    (values (B,), grads (B, 2 + n_ell), objectives {name: (B,)}, info (B,))."""
-    X, y = _problems(X, y)
+def _full_value_and_grad(entry, max_n, X, y, theta, objective, rbf, ctx):
+    X, y = _problems(X, y, max_n)
     B, n, d = X.shape
     th, n_ell = _thetas(theta, B, d)
     code = _objective(objective)
@@ -106,10 +104,18 @@ def value_and_grad_batch(X, y, theta, objective="loo_crps", rbf=False, ctx=None)
     obj = np.empty((B, len(OBJ_NAMES)))
     grad = np.empty((B, 2 + n_ell))
     info = np.zeros(B, np.int32)
-    ctx.call("gps_full_grad_batch", GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
+    ctx.call(entry, GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
              ptr(th), n_ell, ptr(obj), ptr(grad), _iptr(info))
     objs = {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
     return objs[objective], grad, objs, info
+
+
+def value_and_grad_batch(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
+    """Objective value and analytic gradient of B small full GPs at their own θ (one
+    gps_full_grad_batch call; per problem what GP.value_and_grad returns).  Returns
+    (values (B,), grads (B, 2 + n_ell), objectives {name: (B,)}, info (B,))."""
+    return _full_value_and_grad("gps_full_grad_batch", BATCH_MAX_N, X, y, theta, objective, rbf,
+                                ctx)
 
 
 @dataclass
@@ -163,14 +169,8 @@ def _tests(Xt, yt, B, d):
     return Xt, yt, nt
 
 
-def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
-                stale_noise=False, ctx=None):
-    """The reference's SGD fit loop (`itr` steps θ -= lr·grad, KF:236-260) for B small full GPs
-    at once on the device, then one forward at the final kernel parameters with the test
-    predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score bundle against ``yt`` (B, nt).
-    ``stale_noise``: the final pass uses the noise variance of the last step's forward (θ0's
-    with itr = 0), the scripts' module-global sigma_noise_sq (experiment.run_method)."""
-    X, y = _problems(X, y)
+def _full_train(entry, max_n, X, y, theta0, objective, lr, itr, Xt, yt, rbf, stale_noise, ctx):
+    X, y = _problems(X, y, max_n)
     B, n, d = X.shape
     th0, n_ell = _thetas(theta0, B, d)
     code = _objective(objective)
@@ -185,7 +185,7 @@ def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt
     var = np.empty((B, nt)) if nt else None
     sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
     info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call("gps_full_train_batch", GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
+    ctx.call(entry, GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
              ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
              GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(values), ptr(thetas),
              ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
@@ -194,6 +194,35 @@ def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt
         objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
         scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
         info=info, steps_done=steps)
+
+
+def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
+                stale_noise=False, ctx=None):
+    """The reference's SGD fit loop (`itr` steps θ -= lr·grad, KF:236-260) for B small full GPs
+    at once on the device, then one forward at the final kernel parameters with the test
+    predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score bundle against ``yt`` (B, nt).
+    ``stale_noise``: the final pass uses the noise variance of the last step's forward (θ0's
+    with itr = 0), the scripts' module-global sigma_noise_sq (experiment.run_method)."""
+    return _full_train("gps_full_train_batch", BATCH_MAX_N, X, y, theta0, objective, lr, itr, Xt,
+                       yt, rbf, stale_noise, ctx)
+
+
+def value_and_grad_tall(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
+    """value_and_grad_batch for problems of 1 <= n <= 512 training points (one gps_full_grad_tall
+    call, DESIGN §24: one workgroup per problem with the n×n arrays in a device workspace
+    instead of LDS and the O(n³) work on the FP64 matrix instruction).  Same arguments, returns,
+    refusals and ``info``; for n <= 128 the small-batch call is the faster route."""
+    return _full_value_and_grad("gps_full_grad_tall", BATCH_FULL_TALL_MAX_N, X, y, theta,
+                                objective, rbf, ctx)
+
+
+def train_tall(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
+               stale_noise=False, ctx=None):
+    """train_batch for problems of 1 <= n <= 512 training points (one gps_full_train_tall call):
+    the replicate loop of "kin40k-FULL-compare.py" (n = 500, d = 8) for B problems at once.  Same
+    arguments, refusals and BatchTrainResult."""
+    return _full_train("gps_full_train_tall", BATCH_FULL_TALL_MAX_N, X, y, theta0, objective, lr,
+                       itr, Xt, yt, rbf, stale_noise, ctx)
 
 
 def _inducing(Z, B, d):

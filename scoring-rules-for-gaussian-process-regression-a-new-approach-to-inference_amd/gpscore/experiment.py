@@ -15,7 +15,9 @@ and 300 test points (SD:158-181) and makes three fits of each from (1, 1, 1) (SD
 "SIMPLE-FITC--comapre.py" (SF) fits the same data sets with a FITC model of m = 5 inducing inputs
 that are trained too (SF:189-237, 301-343, 420-463): run_simple_fitc, one fitc_train_batch call
 per method.  K20's own LOO-CRPS / NLML / LOO-LogS fits (n = 500, m = 20) go the same way through
-run_fitc_batch, one fitc_train_tall call per method; its DSS and KC fits stay with run.
+run_fitc_batch, one fitc_train_tall call per method; its DSS and KC fits stay with run.  KF's
+LOO-CRPS / NLML / LOO-LogS fits (full GP, n = 500) have a batch route as well: run_full_batch, one
+train_tall call per method for all replicates; its block-LOO DSS and ES fits stay with run.
 
 Every number here comes from gpscore.GP (libgpscore.so): the SGD loops are GP.train, the
 predictive and its scores GP.predict (run_simple: gpscore.batch.train_batch).  The workbook is not shipped (the scripts open it from
@@ -31,7 +33,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
-from .batch import fitc_train_batch, fitc_train_tall, train_batch
+from .batch import fitc_train_batch, fitc_train_tall, train_batch, train_tall
 from .gp import GP
 
 SHEETS = ("trainx", "trainy", "testx", "testy")
@@ -365,5 +367,59 @@ def run_fitc_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=None, resee
                                       f"{int(res.steps_done[q])} steps")
         out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
         out[name]["Z"] = res.Z.copy()
+        out[name]["theta"] = res.theta.copy()
+    return out
+
+
+def run_full_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
+                   stale_noise=True, ctx=None):
+    """KF's replicate loop for its batchable methods → {method: {metric: array(TT), "theta":
+    array(TT, 2 + n_ell)}}: every method's TT full-GP fits (n = 500, the test predictive and the
+    score bundle) are ONE train_tall call, one workgroup per replicate.  ``methods``
+    defaults to the crps / nlml / logs entries of KF_METHODS; a method whose objective is dss or es
+    (block-LOO) has no batched path and raises ValueError (use run(kind="full")).  Data replicates
+    and starting points are drawn in run's order — replicate-major, then method, initial_theta per
+    method — so with the same ``seed``, ``reseed=True`` and the same method subset
+    run(kind="full", methods=subset) and this fit the same problems.  ``itr`` overrides the
+    methods' step counts; stale_noise as run_method.  A replicate whose factorisation fails
+    raises NotPositiveDefinite."""
+    if methods is None:
+        methods = {k: KF_METHODS[k] for k in ("crps", "nlml", "logs")}
+    for name, meth in methods.items():
+        if meth.objective not in BATCH_OBJECTIVES:
+            raise ValueError(f"run_full_batch: method {name!r} has objective {meth.objective!r}, "
+                             f"which has no batched path (only {BATCH_OBJECTIVES}); use "
+                             f"run(kind=\"full\") for it")
+    if int(TT) != TT or TT < 1:
+        raise ValueError(f"TT must be a positive integer, got {TT!r}")
+    TT = int(TT)
+    rng = np.random.default_rng(seed)
+    rs = None if reseed else random.Random()
+    n_pool = sheets["trainx"].shape[0]
+    data, th0 = [], {name: [] for name in methods}
+    for j in range(TT):
+        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
+        data.append(dd)
+        d = dd["train_x"].shape[1]
+        for name, meth in methods.items():
+            k, ell, noise = initial_theta(meth, d, rng)
+            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
+    X = np.stack([dd["train_x"] for dd in data])
+    y = np.stack([dd["train_y"] for dd in data])
+    Xt = np.stack([dd["test_x"] for dd in data])
+    yt = np.stack([dd["test_y"] for dd in data])
+    out = {}
+    for name, meth in methods.items():
+        res = train_tall(X, y, np.stack(th0[name]), meth.objective, lr=meth.lr,
+                         itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
+                         stale_noise=stale_noise, ctx=ctx)
+        bad = np.flatnonzero(res.info)
+        if bad.size:
+            q = int(bad[0])
+            raise NotPositiveDefinite(int(res.info[q]), f"run_full_batch: method {name!r}, "
+                                      f"replicate {q}: the leading minor of order "
+                                      f"{int(res.info[q])} is not positive definite after "
+                                      f"{int(res.steps_done[q])} steps")
+        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
         out[name]["theta"] = res.theta.copy()
     return out
