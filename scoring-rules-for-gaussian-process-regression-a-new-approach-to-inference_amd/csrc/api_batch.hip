@@ -1,40 +1,263 @@
-// C-ABI, batches of small full GPs (n <= 128), one workgroup per problem (kernels_batch.hip):
-// value + gradient of every problem at its own θ, and the SGD fit loops of "SIMPLE-DATA
-// FULL-comapre.py" (SD:192-231, 277-301, 372-396) for a whole batch with the final predictive
-// and score bundle.  The calls own their device buffers (btin, btstate, btint, btout): the
+// C-ABI, the four "one workgroup per problem" batch paths:
+//   gps_full_{grad,train}_batch  small full GPs, n <= 128            kernels_batch.hip
+//   gps_fitc_{grad,train}_batch  small FITC GPs, n <= 128, m <= 32   kernels_batch_fitc.hip
+//   gps_fitc_{grad,train}_tall   FITC GPs, n <= 2048                 kernels_batch_fitc_tall.hip
+//   gps_full_{grad,train}_tall   full GPs, n <= 512                  kernels_batch_full_tall.hip
+// value + gradient of every problem at its own θ (and Z), and the SGD fit loops of the scripts'
+// replicate loops for a whole batch with the final predictive and score bundle.  The calls own
+// their device buffers:
+//   btin     X | y | Xt | yt
+//   btstate  θ (nprob·nth) | stale log σ² (nprob) | Z (nprob·m·d, FITC) | the tall kernels'
+//            per-problem workspace; the full-tall path pads the head to a multiple of 8 doubles
+//            (its workspace is read in 16-byte pieces)
+//   btint    info | steps_done
+//   btout    GRAD: obj | grad | grad_z;  TRAIN: values | thetas | obj | mu | var | sc
+// Every call uploads all it reads, so nothing is carried from one batch call to the next; the
 // resident full-GP / FITC data, any fit and the test buffers are not touched, and nothing is
-// sharded, so a communicator does not matter.
+// sharded, so a communicator does not matter.  A path is one Path constant: its limit on n, its
+// workspace, its steps-per-launch rule, its launcher and its profiling tags; everything else is
+// the two routines grad_call and train_call.
+#include <type_traits>
+
 #include "api_internal.h"
 
 namespace {
 
-int batch_args(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
-               const double* y, int64_t n, int d, const double* theta, int n_ell) {
-  ARGCHK(X && y && theta, "NULL argument");
-  ARGCHK(kind == GPS_ARD || kind == GPS_RBF, "kind must be GPS_ARD or GPS_RBF");
-  ARGCHK(objective == GPS_OBJ_NLML || objective == GPS_OBJ_LOO_CRPS ||
-             objective == GPS_OBJ_LOO_LOGS,
+constexpr int64_t kMaxDoubles = (int64_t)1 << 30;  // 8 GiB of doubles
+const char* const kTooBig = "batch: more than 8 GiB of inputs or outputs, split the batch";
+
+template <class P>
+constexpr bool kFitc = std::is_same<P, BatchFitcParams>::value;
+
+template <class P>
+struct Path {
+  int64_t max_n;
+  const char* n_msg;
+  const char *grad_tag, *train_tag;
+  int64_t (*ws)(int64_t n, int m);  // workspace doubles per problem behind the state, or NULL
+  bool pad;                         // the state's head is padded to a multiple of 8 doubles
+  int (*steps)(int64_t n);          // SGD steps one launch may run
+  hipError_t (*launch)(const P& p, double* ws, int64_t ws_stride, hipStream_t s);
+};
+
+const Path<BatchParams> kFull = {
+    GPS_SURFACE_MAX_N, "batch: n must be in 1..128", "batch_grad", "batch_train", nullptr, false,
+    [](int64_t) { return kBatchStepsPerLaunch; },
+    [](const BatchParams& p, double*, int64_t, hipStream_t s) { return launch_batch(p, s); }};
+const Path<BatchFitcParams> kFitcSmall = {
+    GPS_SURFACE_MAX_N, "batch: n must be in 1..128", "batch_fitc_grad", "batch_fitc_train", nullptr,
+    false, [](int64_t) { return kBatchStepsPerLaunch; },
+    [](const BatchFitcParams& p, double*, int64_t, hipStream_t s) {
+      return launch_batch_fitc(p, s);
+    }};
+const Path<BatchFitcParams> kFitcTall = {
+    GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_grad",
+    "batch_fitc_tall_train", batch_fitc_tall_ws_doubles, false, batch_fitc_tall_steps,
+    [](const BatchFitcParams& p, double* ws, int64_t stride, hipStream_t s) {
+      return launch_batch_fitc_tall(BatchFitcTallParams{p, ws, stride}, s);
+    }};
+const Path<BatchParams> kFullTall = {
+    GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_grad",
+    "batch_full_tall_train", [](int64_t n, int) { return batch_full_tall_ws_doubles(n); }, true,
+    batch_full_tall_steps,
+    [](const BatchParams& p, double* ws, int64_t stride, hipStream_t s) {
+      return launch_batch_full_tall(BatchFullTallParams{p, ws, stride}, s);
+    }};
+
+// what every entry is given; Z and m are NULL and 0, and kind is unused, where the entry has none
+struct Problem {
+  int kind, objective;
+  int64_t nprob;
+  const double *X, *y;
+  int64_t n;
+  int d;
+  const double* Z;
+  int m;
+  const double* theta;
+  int n_ell;
+};
+
+template <class P>
+int check_problem(gps_ctx* ctx, const Path<P>& path, const Problem& a) {
+  ARGCHK(a.X && a.y && (!kFitc<P> || a.Z) && a.theta, "NULL argument");
+  if (!kFitc<P>) ARGCHK(a.kind == GPS_ARD || a.kind == GPS_RBF, "kind must be GPS_ARD or GPS_RBF");
+  ARGCHK(a.objective == GPS_OBJ_NLML || a.objective == GPS_OBJ_LOO_CRPS ||
+             a.objective == GPS_OBJ_LOO_LOGS,
          "objective must be GPS_OBJ_NLML, GPS_OBJ_LOO_CRPS or GPS_OBJ_LOO_LOGS");
-  ARGCHK(nprob >= 1 && nprob <= (1 << 20), "batch: nprob must be in 1..2^20");
-  ARGCHK(n >= 1 && n <= GPS_SURFACE_MAX_N, "batch: n must be in 1..128");
-  ARGCHK(d >= 1 && d <= GPS_BATCH_MAX_D, "batch: d must be in 1..16");
-  ARGCHK(n_ell == 1 || n_ell == d, "n_ell must be 1 or d");
+  ARGCHK(a.nprob >= 1 && a.nprob <= (1 << 20), "batch: nprob must be in 1..2^20");
+  ARGCHK(a.n >= 1 && a.n <= path.max_n, path.n_msg);
+  if (kFitc<P>) ARGCHK(a.m >= 1 && a.m <= GPS_BATCH_FITC_MAX_M, "batch: m must be in 1..32");
+  ARGCHK(a.d >= 1 && a.d <= GPS_BATCH_MAX_D, "batch: d must be in 1..16");
+  ARGCHK(a.n_ell == 1 || a.n_ell == a.d, "n_ell must be 1 or d");
   return 0;
 }
 
-BatchParams batch_params(gps_ctx* ctx, int kind, int objective, int64_t nprob, int64_t n, int d,
-                         int n_ell) {
-  BatchParams p;
+// Sizes the four buffers (nt test rows a problem, n_out output doubles, n_ws workspace doubles in
+// all) and fills p with the problem and the carving of btin, btstate and btint; *ws is the
+// workspace behind the state's head.
+template <class P>
+int carve(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t nt, int64_t n_out,
+          int64_t n_ws, P& p, double** ws) {
+  const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
+  int64_t head = nprob * (nth + 1 + nz);
+  if (path.pad) head = (head + 7) / 8 * 8;
+  HIPCHK(ensure(ctx, ctx->btin, (size_t)(nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1)) * 8));
+  HIPCHK(ensure(ctx, ctx->btstate, (size_t)(head + n_ws) * 8));
+  HIPCHK(ensure(ctx, ctx->btint, (size_t)(2 * nprob) * sizeof(int)));
+  HIPCHK(ensure(ctx, ctx->btout, (size_t)n_out * 8));
   memset(&p, 0, sizeof(p));
-  p.nprob = (int)nprob; p.n = (int)n; p.d = d; p.n_ell = n_ell; p.kind = kind;
-  p.objective = objective;
+  p.nprob = (int)nprob; p.n = (int)a.n; p.d = a.d; p.n_ell = a.n_ell;
+  p.objective = a.objective;
   p.x = ctx->btin.d();
-  p.y = p.x + nprob * n * d;
+  p.y = p.x + nprob * a.n * a.d;
   p.theta = ctx->btstate.d();
-  p.stale = p.theta + nprob * (2 + n_ell);
+  p.stale = p.theta + nprob * nth;
+  if constexpr (kFitc<P>) {
+    p.m = a.m;
+    p.z = p.stale + nprob;
+  } else {
+    p.kind = a.kind;
+  }
   p.info = static_cast<int*>(ctx->btint.p);
   p.steps_done = p.info + nprob;
-  return p;
+  *ws = p.theta + head;
+  return 0;
+}
+
+// X, y, the test rows where given, θ, Z and the stale σ² (zero without `stale`) to the device;
+// info and steps_done start at zero
+template <class P>
+int upload(gps_ctx* ctx, const Problem& a, const P& p, const double* Xt, const double* yt,
+           const double* stale) {
+  const int64_t nprob = a.nprob, nth = 2 + a.n_ell;
+  hipStream_t s = ctx->stream;
+  HIPCHK(hipMemcpyAsync((void*)p.x, a.X, (size_t)(nprob * a.n * a.d) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync((void*)p.y, a.y, (size_t)(nprob * a.n) * 8, hipMemcpyHostToDevice, s));
+  if (p.xt)
+    HIPCHK(hipMemcpyAsync((void*)p.xt, Xt, (size_t)(nprob * p.nt * a.d) * 8, hipMemcpyHostToDevice,
+                          s));
+  if (p.yt)
+    HIPCHK(hipMemcpyAsync((void*)p.yt, yt, (size_t)(nprob * p.nt) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(p.theta, a.theta, (size_t)(nprob * nth) * 8, hipMemcpyHostToDevice, s));
+  if constexpr (kFitc<P>)
+    HIPCHK(hipMemcpyAsync(p.z, a.Z, (size_t)(nprob * a.m * a.d) * 8, hipMemcpyHostToDevice, s));
+  if (stale)
+    HIPCHK(hipMemcpyAsync(p.stale, stale, (size_t)nprob * 8, hipMemcpyHostToDevice, s));
+  else
+    HIPCHK(hipMemsetAsync(p.stale, 0, (size_t)nprob * 8, s));
+  HIPCHK(hipMemsetAsync(p.info, 0, (size_t)(2 * nprob) * sizeof(int), s));
+  return 0;
+}
+
+// count elements of T back to the host; an output that is NULL or empty is skipped
+template <class T>
+int download(gps_ctx* ctx, T* dst, const T* src, int64_t count) {
+  if (dst && count > 0)
+    HIPCHK(hipMemcpyAsync(dst, src, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
+}
+
+template <class P>
+int grad_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, double* obj, double* grad,
+              double* grad_z, int* info) {
+  if (int rc = bind(ctx)) return rc;
+  if (int rc = check_problem(ctx, path, a)) return rc;
+  ARGCHK(grad && (!kFitc<P> || grad_z) && info, "NULL argument");
+  const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
+  const int64_t stride = path.ws ? path.ws(a.n, a.m) : 0, n_ws = nprob * stride;
+  if (path.ws)  // the small paths' value + gradient calls have no such guard
+    ARGCHK(nprob * a.n * (a.d + 1) + nprob * nz <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
+  P p;
+  double* ws;
+  if (int rc = carve(ctx, path, a, 0, nprob * (GPS_N_OBJ + nth + nz), n_ws, p, &ws)) return rc;
+  p.mode = BATCH_MODE_GRAD;
+  p.obj = ctx->btout.d();
+  p.grad = p.obj + nprob * GPS_N_OBJ;
+  if constexpr (kFitc<P>) p.grad_z = p.grad + nprob * nth;
+  if (int rc = upload(ctx, a, p, nullptr, nullptr, nullptr)) return rc;
+  {
+    Prof pr(ctx, path.grad_tag, 0, 0);
+    HIPCHK(path.launch(p, ws, stride, ctx->stream));
+  }
+  if (int rc = download(ctx, obj, p.obj, nprob * GPS_N_OBJ)) return rc;
+  if (int rc = download(ctx, grad, p.grad, nprob * nth)) return rc;
+  if constexpr (kFitc<P>)
+    if (int rc = download(ctx, grad_z, p.grad_z, nprob * nz)) return rc;
+  if (int rc = download(ctx, info, p.info, nprob)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+template <class P>
+int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr, double lr,
+               double lr_z, const double* Xt, const double* yt, int64_t nt, int flags,
+               double* theta_out, double* z_out, double* values, double* thetas, double* obj,
+               double* mu, double* var, double* sc, int* info, int* steps_done) {
+  if (int rc = bind(ctx)) return rc;
+  if (int rc = check_problem(ctx, path, a)) return rc;
+  ARGCHK(theta_out && (!kFitc<P> || z_out) && info && steps_done, "NULL argument");
+  ARGCHK(itr >= 0 && itr <= (1 << 20), "batch: itr must be in 0..2^20");
+  ARGCHK(std::isfinite(lr), "batch: lr must be finite");
+  if (kFitc<P>) ARGCHK(std::isfinite(lr_z), "batch: lr_z must be finite");
+  ARGCHK(nt >= 0 && nt <= (1 << 24), "batch: nt must be in 0..2^24");
+  ARGCHK((flags & ~GPS_BATCH_STALE_NOISE) == 0, "unknown batch flag");
+  const bool pred = Xt != nullptr && nt > 0;
+  if (!pred) nt = 0;
+  const bool scored = pred && yt != nullptr;
+  const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
+  const int64_t n_in = nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + nprob * nz;
+  const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC);
+  const int64_t stride = path.ws ? path.ws(a.n, a.m) : 0, n_ws = nprob * stride;
+  ARGCHK(n_in <= kMaxDoubles && n_out <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
+  P p;
+  double* ws;
+  if (int rc = carve(ctx, path, a, nt, n_out, n_ws, p, &ws)) return rc;
+  p.mode = BATCH_MODE_TRAIN;
+  p.itr = (int)itr;
+  p.lr = lr;
+  if constexpr (kFitc<P>) p.lr_z = lr_z;
+  p.stale_noise = (flags & GPS_BATCH_STALE_NOISE) != 0;
+  p.nt = (int)nt;
+  const double* xt_dev = p.y + nprob * a.n;
+  p.xt = pred ? xt_dev : nullptr;
+  p.yt = scored ? xt_dev + nprob * nt * a.d : nullptr;
+  p.values = ctx->btout.d();
+  p.thetas = p.values + nprob * itr;
+  p.obj = p.thetas + nprob * itr * nth;
+  p.mu = p.obj + nprob * GPS_N_OBJ;
+  p.var = p.mu + nprob * nt;
+  p.sc = p.var + nprob * nt;
+  std::vector<double> stale((size_t)nprob);  // before any step: θ0's own noise
+  for (int64_t q = 0; q < nprob; ++q) stale[(size_t)q] = a.theta[q * nth + nth - 1];
+  if (int rc = upload(ctx, a, p, Xt, yt, stale.data())) return rc;
+  {
+    // no launch runs more than path.steps(n) steps; θ, Z, the stale σ², info and steps_done stay
+    // in device memory between the launches, the last one adds the final pass
+    Prof pr(ctx, path.train_tag, 0, 0);
+    const int64_t per = path.steps(a.n);
+    int64_t step = 0;
+    do {
+      const int64_t ns = std::min<int64_t>(itr - step, per);
+      p.step0 = (int)step;
+      p.nsteps = (int)ns;
+      p.do_final = step + ns == itr;
+      HIPCHK(path.launch(p, ws, stride, ctx->stream));
+      step += ns;
+    } while (step < itr);
+  }
+  if (int rc = download(ctx, theta_out, p.theta, nprob * nth)) return rc;
+  if constexpr (kFitc<P>)
+    if (int rc = download(ctx, z_out, p.z, nprob * nz)) return rc;
+  if (int rc = download(ctx, values, p.values, nprob * itr)) return rc;
+  if (int rc = download(ctx, thetas, p.thetas, nprob * itr * nth)) return rc;
+  if (int rc = download(ctx, obj, p.obj, nprob * GPS_N_OBJ)) return rc;
+  if (int rc = download(ctx, mu, p.mu, nprob * nt)) return rc;
+  if (int rc = download(ctx, var, p.var, nprob * nt)) return rc;
+  if (int rc = download(ctx, scored ? sc : nullptr, p.sc, nprob * GPS_N_SC)) return rc;
+  if (int rc = download(ctx, info, p.info, nprob)) return rc;
+  if (int rc = download(ctx, steps_done, p.steps_done, nprob)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 }  // namespace
@@ -44,34 +267,8 @@ extern "C" {
 int gps_full_grad_batch(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
                         const double* y, int64_t n, int d, const double* theta, int n_ell,
                         double* obj, double* grad, int* info) {
-  if (int rc = bind(ctx)) return rc;
-  if (int rc = batch_args(ctx, kind, objective, nprob, X, y, n, d, theta, n_ell)) return rc;
-  ARGCHK(grad && info, "NULL argument");
-  const int64_t nth = 2 + n_ell;
-  hipStream_t s = ctx->stream;
-  HIPCHK(ensure(ctx, ctx->btin, (size_t)(nprob * n * (d + 1)) * 8));
-  HIPCHK(ensure(ctx, ctx->btstate, (size_t)(nprob * (nth + 1)) * 8));
-  HIPCHK(ensure(ctx, ctx->btint, (size_t)(2 * nprob) * sizeof(int)));
-  HIPCHK(ensure(ctx, ctx->btout, (size_t)(nprob * (GPS_N_OBJ + nth)) * 8));
-  BatchParams p = batch_params(ctx, kind, objective, nprob, n, d, n_ell);
-  p.mode = BATCH_MODE_GRAD;
-  p.obj = ctx->btout.d();
-  p.grad = p.obj + nprob * GPS_N_OBJ;
-  HIPCHK(hipMemcpyAsync((void*)p.x, X, (size_t)(nprob * n * d) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync((void*)p.y, y, (size_t)(nprob * n) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(p.theta, theta, (size_t)(nprob * nth) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(p.stale, 0, (size_t)nprob * 8, s));
-  HIPCHK(hipMemsetAsync(p.info, 0, (size_t)(2 * nprob) * sizeof(int), s));
-  {
-    Prof pr(ctx, "batch_grad", 0, 0);
-    HIPCHK(launch_batch(p, s));
-  }
-  if (obj)
-    HIPCHK(hipMemcpyAsync(obj, p.obj, (size_t)(nprob * GPS_N_OBJ) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(grad, p.grad, (size_t)(nprob * nth) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(info, p.info, (size_t)nprob * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return grad_call(ctx, kFull, {kind, objective, nprob, X, y, n, d, nullptr, 0, theta, n_ell}, obj,
+                   grad, nullptr, info);
 }
 
 int gps_full_train_batch(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
@@ -79,86 +276,66 @@ int gps_full_train_batch(gps_ctx* ctx, int kind, int objective, int64_t nprob, c
                          int64_t itr, double lr, const double* Xt, const double* yt, int64_t nt,
                          int flags, double* theta_out, double* values, double* thetas, double* obj,
                          double* mu, double* var, double* sc, int* info, int* steps_done) {
-  if (int rc = bind(ctx)) return rc;
-  if (int rc = batch_args(ctx, kind, objective, nprob, X, y, n, d, theta0, n_ell)) return rc;
-  ARGCHK(theta_out && info && steps_done, "NULL argument");
-  ARGCHK(itr >= 0 && itr <= (1 << 20), "batch: itr must be in 0..2^20");
-  ARGCHK(std::isfinite(lr), "batch: lr must be finite");
-  ARGCHK(nt >= 0 && nt <= (1 << 24), "batch: nt must be in 0..2^24");
-  ARGCHK((flags & ~GPS_BATCH_STALE_NOISE) == 0, "unknown batch flag");
-  const bool pred = Xt != nullptr && nt > 0;
-  if (!pred) nt = 0;
-  const bool scored = pred && yt != nullptr;
-  const int64_t nth = 2 + n_ell;
-  const int64_t n_in = nprob * n * (d + 1) + nprob * nt * (d + 1);
-  const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC);
-  ARGCHK(n_in <= ((int64_t)1 << 30) && n_out <= ((int64_t)1 << 30),
-         "batch: more than 8 GiB of inputs or outputs, split the batch");
-  hipStream_t s = ctx->stream;
-  HIPCHK(ensure(ctx, ctx->btin, (size_t)n_in * 8));
-  HIPCHK(ensure(ctx, ctx->btstate, (size_t)(nprob * (nth + 1)) * 8));
-  HIPCHK(ensure(ctx, ctx->btint, (size_t)(2 * nprob) * sizeof(int)));
-  HIPCHK(ensure(ctx, ctx->btout, (size_t)n_out * 8));
-  BatchParams p = batch_params(ctx, kind, objective, nprob, n, d, n_ell);
-  p.mode = BATCH_MODE_TRAIN;
-  p.itr = (int)itr;
-  p.lr = lr;
-  p.stale_noise = (flags & GPS_BATCH_STALE_NOISE) != 0;
-  p.nt = (int)nt;
-  double* xt_dev = const_cast<double*>(p.y) + nprob * n;
-  double* yt_dev = xt_dev + nprob * nt * d;
-  p.xt = pred ? xt_dev : nullptr;
-  p.yt = scored ? yt_dev : nullptr;
-  p.values = ctx->btout.d();
-  p.thetas = p.values + nprob * itr;
-  p.obj = p.thetas + nprob * itr * nth;
-  p.mu = p.obj + nprob * GPS_N_OBJ;
-  p.var = p.mu + nprob * nt;
-  p.sc = p.var + nprob * nt;
-  std::vector<double> stale((size_t)nprob);  // before any step: θ0's own noise
-  for (int64_t q = 0; q < nprob; ++q) stale[(size_t)q] = theta0[q * nth + nth - 1];
-  HIPCHK(hipMemcpyAsync((void*)p.x, X, (size_t)(nprob * n * d) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync((void*)p.y, y, (size_t)(nprob * n) * 8, hipMemcpyHostToDevice, s));
-  if (pred)
-    HIPCHK(hipMemcpyAsync(xt_dev, Xt, (size_t)(nprob * nt * d) * 8, hipMemcpyHostToDevice, s));
-  if (scored)
-    HIPCHK(hipMemcpyAsync(yt_dev, yt, (size_t)(nprob * nt) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(p.theta, theta0, (size_t)(nprob * nth) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(p.stale, stale.data(), (size_t)nprob * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(p.info, 0, (size_t)(2 * nprob) * sizeof(int), s));
-  {
-    // no launch runs more than kBatchStepsPerLaunch steps; θ, the stale σ², info and steps_done
-    // stay in device memory between the launches, the last one adds the final pass
-    Prof pr(ctx, "batch_train", 0, 0);
-    int64_t step = 0;
-    do {
-      const int64_t ns = std::min<int64_t>(itr - step, kBatchStepsPerLaunch);
-      p.step0 = (int)step;
-      p.nsteps = (int)ns;
-      p.do_final = step + ns == itr;
-      HIPCHK(launch_batch(p, s));
-      step += ns;
-    } while (step < itr);
-  }
-  HIPCHK(hipMemcpyAsync(theta_out, p.theta, (size_t)(nprob * nth) * 8, hipMemcpyDeviceToHost, s));
-  if (values && itr)
-    HIPCHK(hipMemcpyAsync(values, p.values, (size_t)(nprob * itr) * 8, hipMemcpyDeviceToHost, s));
-  if (thetas && itr)
-    HIPCHK(hipMemcpyAsync(thetas, p.thetas, (size_t)(nprob * itr * nth) * 8, hipMemcpyDeviceToHost,
-                          s));
-  if (obj)
-    HIPCHK(hipMemcpyAsync(obj, p.obj, (size_t)(nprob * GPS_N_OBJ) * 8, hipMemcpyDeviceToHost, s));
-  if (pred && mu)
-    HIPCHK(hipMemcpyAsync(mu, p.mu, (size_t)(nprob * nt) * 8, hipMemcpyDeviceToHost, s));
-  if (pred && var)
-    HIPCHK(hipMemcpyAsync(var, p.var, (size_t)(nprob * nt) * 8, hipMemcpyDeviceToHost, s));
-  if (scored && sc)
-    HIPCHK(hipMemcpyAsync(sc, p.sc, (size_t)(nprob * GPS_N_SC) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(info, p.info, (size_t)nprob * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(steps_done, p.steps_done, (size_t)nprob * sizeof(int),
-                        hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
+  return train_call(ctx, kFull, {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell},
+                    itr, lr, 0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu,
+                    var, sc, info, steps_done);
+}
+
+int gps_full_grad_tall(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                       const double* y, int64_t n, int d, const double* theta, int n_ell,
+                       double* obj, double* grad, int* info) {
+  return grad_call(ctx, kFullTall, {kind, objective, nprob, X, y, n, d, nullptr, 0, theta, n_ell},
+                   obj, grad, nullptr, info);
+}
+
+int gps_full_train_tall(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* theta0, int n_ell,
+                        int64_t itr, double lr, const double* Xt, const double* yt, int64_t nt,
+                        int flags, double* theta_out, double* values, double* thetas, double* obj,
+                        double* mu, double* var, double* sc, int* info, int* steps_done) {
+  return train_call(ctx, kFullTall, {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell},
+                    itr, lr, 0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu,
+                    var, sc, info, steps_done);
+}
+
+int gps_fitc_grad_batch(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* Z, int m,
+                        const double* theta, int n_ell, double* obj, double* grad, double* grad_z,
+                        int* info) {
+  return grad_call(ctx, kFitcSmall, {0, objective, nprob, X, y, n, d, Z, m, theta, n_ell}, obj,
+                   grad, grad_z, info);
+}
+
+int gps_fitc_train_batch(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                         const double* y, int64_t n, int d, const double* Z0, int m,
+                         const double* theta0, int n_ell, int64_t itr, double lr, double lr_z,
+                         const double* Xt, const double* yt, int64_t nt, int flags,
+                         double* theta_out, double* z_out, double* values, double* thetas,
+                         double* obj, double* mu, double* var, double* sc, int* info,
+                         int* steps_done) {
+  return train_call(ctx, kFitcSmall, {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell}, itr,
+                    lr, lr_z, Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc,
+                    info, steps_done);
+}
+
+int gps_fitc_grad_tall(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                       const double* y, int64_t n, int d, const double* Z, int m,
+                       const double* theta, int n_ell, double* obj, double* grad, double* grad_z,
+                       int* info) {
+  return grad_call(ctx, kFitcTall, {0, objective, nprob, X, y, n, d, Z, m, theta, n_ell}, obj, grad,
+                   grad_z, info);
+}
+
+int gps_fitc_train_tall(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                        const double* y, int64_t n, int d, const double* Z0, int m,
+                        const double* theta0, int n_ell, int64_t itr, double lr, double lr_z,
+                        const double* Xt, const double* yt, int64_t nt, int flags,
+                        double* theta_out, double* z_out, double* values, double* thetas,
+                        double* obj, double* mu, double* var, double* sc, int* info,
+                        int* steps_done) {
+  return train_call(ctx, kFitcTall, {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell}, itr,
+                    lr, lr_z, Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc,
+                    info, steps_done);
 }
 
 }  // extern "C"

@@ -4,8 +4,8 @@
 // launch helpers, the recursive factorisation driver, L1 blocks), api_full.hip (full GP, CP.R
 // surfaces), api_fitc.hip (FITC fit / gradients / predict), api_block.hip (block-LOO and the
 // energy score), api_joint.hip (the joint test predictive: full covariance, DSS / ES test scores,
-// draws), api_batch.hip (batches of small full GPs, one workgroup each), api_batch_fitc.hip (the
-// same for small FITC GPs), api_comm.hip (RCCL and the in-process communicator).
+// draws), api_batch.hip (the four batch paths, one workgroup per problem: small and tall, full
+// GP and FITC), api_comm.hip (RCCL and the in-process communicator).
 #pragma once
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -218,8 +218,8 @@ struct gps_ctx {
   // slabs when the stream's workspace is too small, Sigma_b, its L⁻¹ / L / factorisation workspace,
   // vectors and scalars, the ES work area and draws, the padded ξ and the draws' product
   DBuf jK, jV, jslab, jS, jL, jLo, jW, jvec, jE, jdraws, jxi, jout;
-  // batched small GPs (api_batch.hip), the calls' own: inputs (X | y | Xt | yt), per-problem state
-  // (θ | stale log σ²), its ints (info | steps_done), outputs (series, objectives, predictive)
+  // batches of GPs (api_batch.hip), the calls' own: inputs (X | y | Xt | yt), per-problem state
+  // (θ | stale log σ² | Z | workspace), its ints (info | steps_done), outputs (series, objectives, predictive)
   DBuf btin, btstate, btint, btout;
   int64_t fn = 0, fn_pad = 0, fnt = 0, fnt_pad = 0, m = 0, m_pad = 0, fn_total = 0, fnt_total = 0;
   int fd = 0;

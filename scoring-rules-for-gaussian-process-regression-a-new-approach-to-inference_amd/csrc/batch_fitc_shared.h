@@ -3,6 +3,7 @@
 // (the n-sized arrays in a device workspace, n <= 2048).  Included once per kernel
 // file; everything sits in that file's anonymous namespace.
 #pragma once
+#include "batch_driver.h"
 #include "gps_internal.h"
 #include "gpscore.h"
 
@@ -97,6 +98,18 @@ __device__ __forceinline__ int chol_inv(double* W, int m, int ld, double* piv, d
   }
   __syncthreads();
   return 0;
+}
+
+// BATCH_MODE_GRAD's end for the FITC pair: NaN for a failed problem, and info
+__device__ __forceinline__ void fitc_grad_end(const BatchFitcParams p, int64_t pb, int t,
+                                              int info) {
+  const int m = p.m, d = p.d, nth = 2 + p.n_ell;
+  if (info) {
+    if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = batch_nan();
+    if (t < nth) p.grad[pb * nth + t] = batch_nan();
+    for (int e = t; e < m * d; e += FT) p.grad_z[pb * m * d + e] = batch_nan();
+  }
+  if (t == 0) p.info[pb] = info;
 }
 
 }  // namespace

@@ -360,6 +360,9 @@ int batch_full_tall_steps(int64_t n);
 hipError_t launch_batch_full_tall(const BatchFullTallParams& p, hipStream_t s);
 
 // ------------------------------------------------------------------ launchers
+// raises `kernel`'s dynamic-LDS limit to `bytes` on the current device, once per (device, kernel)
+// (kernels_surface.hip); every launcher of a kernel that may need more than 64 KB calls it first
+hipError_t raise_dynamic_lds(const void* kernel, size_t bytes);
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 hipError_t launch_batch(const BatchParams& p, hipStream_t s);
 hipError_t launch_batch_fitc(const BatchFitcParams& p, hipStream_t s);

@@ -22,9 +22,7 @@
 // The k loops are LDS-bandwidth bound (plain FP64 FMAs from LDS, not the MFMA: DESIGN §19).
 // Every reduction order is a function of n, d and the 256 threads only: results are bitwise
 // reproducible and independent of the batch size, the problem's position and the launch split.
-#include <mutex>
-#include <set>
-
+#include "batch_driver.h"
 #include "gps_internal.h"
 #include "gpscore.h"
 
@@ -339,7 +337,6 @@ __global__ __launch_bounds__(BT) void batch_kernel(BatchParams p) {
   const int nth = 2 + p.n_ell;
   const int64_t pb = blockIdx.x;
   const Lds s = carve(sm, n, d);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   double* il = s.th + 20;
   int info = p.info[pb];
   int done = p.steps_done[pb];
@@ -357,14 +354,7 @@ __global__ __launch_bounds__(BT) void batch_kernel(BatchParams p) {
   double sf2 = 0.0, sn2 = 0.0;
   for (int st = 0; st < neval && info == 0; ++st) {
     const bool fin = st == ntrain;
-    __syncthreads();  // θ (loaded, or the previous step's update) is visible
-    const double lsn = s.th[nth - 1];
-    sf2 = exp(s.th[0]);
-    sn2 = exp(fin && p.stale_noise ? stale : lsn);
-    const double bq = t < d ? s.th[1 + (p.n_ell == 1 ? 0 : t)] : 0.0;
-    if (t < d) il[t] = p.kind == GPS_ARD ? exp(-bq) : exp(-0.5 * bq);
-    __syncthreads();
-    if (!fin) stale = lsn;
+    step_prologue(p, t, s.th, il, p.kind, fin, stale, sf2, sn2);
     info = forward(s, n, d, sf2, sn2, obj);
     if (info || fin) break;
     double g[BG];
@@ -410,48 +400,17 @@ __global__ __launch_bounds__(BT) void batch_kernel(BatchParams p) {
   __syncthreads();
 
   if (p.mode == BATCH_MODE_GRAD) {
-    if (t == 0) {
-      p.info[pb] = info;
-      if (info) {
-        for (int q = 0; q < GPS_N_OBJ; ++q) p.obj[pb * GPS_N_OBJ + q] = nan;
-        for (int q = 0; q < nth; ++q) p.grad[pb * nth + q] = nan;
-      }
-    }
+    full_grad_end(p, pb, t, info);
     return;
   }
-  // a failed problem (in this launch or an earlier one): NaN in the rest of its series
-  if (info) {
-    const int s0 = done > p.step0 ? done : p.step0;
-    const int s1 = p.step0 + p.nsteps;
-    for (int e = s0 + t; e < s1; e += BT) p.values[pb * p.itr + e] = nan;
-    for (int64_t e = (int64_t)s0 * nth + t; e < (int64_t)s1 * nth; e += BT)
-      p.thetas[pb * p.itr * nth + e] = nan;
-  }
-  if (t < nth) p.theta[pb * nth + t] = s.th[t];
-  if (t == 0) {
-    p.stale[pb] = stale;
-    p.steps_done[pb] = done;
-  }
+  train_write_back<BT>(p, pb, t, s.th, nullptr, info, done, stale);
   if (!p.do_final) {
     if (t == 0) p.info[pb] = info;
     return;
   }
   if (t == 0) p.info[pb] = info;
   const bool pred = p.xt != nullptr && p.nt > 0;
-  if (info) {
-    if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = nan;
-    if (pred) {
-      for (int e = t; e < p.nt; e += BT) {
-        p.mu[pb * p.nt + e] = nan;
-        p.var[pb * p.nt + e] = nan;
-      }
-      if (p.yt && t < GPS_N_SC) p.sc[pb * GPS_N_SC + t] = nan;
-    }
-    return;
-  }
-  if (t == 0)
-    for (int q = 0; q < GPS_N_OBJ; ++q) p.obj[pb * GPS_N_OBJ + q] = obj[q];
-  if (!pred) return;
+  if (!final_outputs<BT>(p, pb, t, info, pred, obj)) return;
   // train-target mean and unbiased variance, in gps_full_set_data's order
   double ysum = 0.0, yss = 0.0;
   for (int i = 0; i < n; ++i) ysum += s.y[i];
@@ -504,15 +463,7 @@ __global__ __launch_bounds__(BT) void batch_kernel(BatchParams p) {
       }
       if (p.yt) {
         const double yv = p.yt[pb * p.nt + row];
-        sums[0] += crps_term(mu, c, yv);
-        const double ls = logs_term(mu, c, yv);
-        sums[1] += ls;
-        const double e0 = yv - ymean;
-        sums[2] += ls - (triv_c + e0 * e0 / (2.0 * yvar));
-        sums[3] += (mu - yv) * (mu - yv);
-        sums[4] += e0 * e0;
-        const double sd = sqrt(c);
-        sums[5] += ((mu + 2.0 * sd - yv) > 0.0 && (yv - (mu - 2.0 * sd)) > 0.0) ? 1.0 : 0.0;
+        score_row_add(sums, mu, c, yv, ymean, yvar, triv_c);
       }
     }
     __syncthreads();
@@ -528,14 +479,7 @@ __global__ __launch_bounds__(BT) void batch_kernel(BatchParams p) {
       for (int w = 0; w < BT / 64; ++w) a += s.sh[q * 16 + w];
       tot[q] = a;
     }
-    const double nt = (double)p.nt;
-    double* sc = p.sc + pb * GPS_N_SC;
-    sc[GPS_SC_CRPS] = tot[0] / nt;
-    sc[GPS_SC_LOGS] = tot[1] / nt;
-    sc[GPS_SC_MSLL] = tot[2] / nt;
-    sc[GPS_SC_SMSE] = tot[3] / tot[4];
-    sc[GPS_SC_MSE] = tot[3] / nt;
-    sc[GPS_SC_COVER] = tot[5] / nt;
+    scores_store(p, pb, tot);
   }
 }
 
@@ -549,22 +493,9 @@ hipError_t launch_batch(const BatchParams& p, hipStream_t s) {
   if (p.n < 1 || p.n > GPS_SURFACE_MAX_N || p.d < 1 || p.d > GPS_BATCH_MAX_D || p.nprob < 1 ||
       (p.n_ell != 1 && p.n_ell != p.d) || p.nsteps < 0 || p.nsteps > kBatchStepsPerLaunch)
     return hipErrorInvalidValue;
-  // the dynamic-LDS limit is a per-device function attribute: set once per device under a lock
-  // (as launch_surface)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = raise_dynamic_lds(
+      (const void*)batch_kernel, batch_lds_bytes(GPS_SURFACE_MAX_N, GPS_BATCH_MAX_D));
   if (e != hipSuccess) return e;
-  {
-    static std::mutex mu;
-    static std::set<int> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      e = hipFuncSetAttribute((const void*)batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)batch_lds_bytes(GPS_SURFACE_MAX_N, GPS_BATCH_MAX_D));
-      if (e != hipSuccess) return e;
-      done.insert(dev);
-    }
-  }
   hipLaunchKernelGGL(batch_kernel, dim3((unsigned)p.nprob), dim3(BT), batch_lds_bytes(p.n, p.d), s,
                      p);
   return hipGetLastError();

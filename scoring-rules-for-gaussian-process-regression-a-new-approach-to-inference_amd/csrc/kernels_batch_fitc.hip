@@ -27,9 +27,6 @@
 // batch size, the problem's position and the launch split.  Every loop bound is a function of
 // n, m, d, nt and nsteps; every exit is workgroup-uniform (the pivots are read from LDS by all).
 // Plain FP64 FMAs: at SF's m = 5 a step is barrier- and latency-bound.
-#include <mutex>
-#include <set>
-
 #include "batch_fitc_shared.h"  // FT, FG, odd_ld, group_lanes, group_sum, block_sum_n, chol_inv
 #include "gps_internal.h"
 #include "gpscore.h"
@@ -367,7 +364,6 @@ __global__ __launch_bounds__(FT) void batch_fitc_kernel(BatchFitcParams p) {
   const int nth = 2 + p.n_ell;
   const int64_t pb = blockIdx.x;
   const Lds s = carve(sm, n, m, d);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   double* il = s.th + 20;
   int info = p.info[pb];
   int done = p.steps_done[pb];
@@ -385,14 +381,7 @@ __global__ __launch_bounds__(FT) void batch_fitc_kernel(BatchFitcParams p) {
   double sf2 = 0.0, sn2 = 0.0;
   for (int st = 0; st < neval && info == 0; ++st) {
     const bool fin = st == ntrain;
-    __syncthreads();  // θ and Z (loaded, or the previous step's update) are visible
-    const double lsn = s.th[nth - 1];
-    sf2 = exp(s.th[0]);
-    sn2 = exp(fin && p.stale_noise ? stale : lsn);
-    const double bq = t < d ? s.th[1 + (p.n_ell == 1 ? 0 : t)] : 0.0;
-    if (t < d) il[t] = exp(-bq);  // th + 20: beside θ, never over it
-    __syncthreads();
-    if (!fin) stale = lsn;
+    step_prologue(p, t, s.th, il, GPS_ARD, fin, stale, sf2, sn2);
     info = forward(s, n, m, d, sf2, sn2, obj);
     if (info || fin) break;
     double g[FG], gz[GPS_BATCH_MAX_D];
@@ -458,45 +447,14 @@ __global__ __launch_bounds__(FT) void batch_fitc_kernel(BatchFitcParams p) {
   __syncthreads();
 
   if (p.mode == BATCH_MODE_GRAD) {
-    if (info) {
-      if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = nan;
-      if (t < nth) p.grad[pb * nth + t] = nan;
-      for (int e = t; e < m * d; e += FT) p.grad_z[pb * m * d + e] = nan;
-    }
-    if (t == 0) p.info[pb] = info;
+    fitc_grad_end(p, pb, t, info);
     return;
   }
-  // a failed problem (in this launch or an earlier one): NaN in the rest of its series
-  if (info) {
-    const int s0 = done > p.step0 ? done : p.step0;
-    const int s1 = p.step0 + p.nsteps;
-    for (int e = s0 + t; e < s1; e += FT) p.values[pb * p.itr + e] = nan;
-    for (int64_t e = (int64_t)s0 * nth + t; e < (int64_t)s1 * nth; e += FT)
-      p.thetas[pb * p.itr * nth + e] = nan;
-  }
-  if (t < nth) p.theta[pb * nth + t] = s.th[t];
-  for (int e = t; e < m * d; e += FT) p.z[pb * m * d + e] = s.zs[e];
-  if (t == 0) {
-    p.stale[pb] = stale;
-    p.steps_done[pb] = done;
-    p.info[pb] = info;
-  }
+  train_write_back<FT>(p, pb, t, s.th, s.zs, info, done, stale);
+  if (t == 0) p.info[pb] = info;
   if (!p.do_final) return;
   const bool pred = p.xt != nullptr && p.nt > 0;
-  if (info) {
-    if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = nan;
-    if (pred) {
-      for (int e = t; e < p.nt; e += FT) {
-        p.mu[pb * p.nt + e] = nan;
-        p.var[pb * p.nt + e] = nan;
-      }
-      if (p.yt && t < GPS_N_SC) p.sc[pb * GPS_N_SC + t] = nan;
-    }
-    return;
-  }
-  if (t == 0)
-    for (int q = 0; q < GPS_N_OBJ; ++q) p.obj[pb * GPS_N_OBJ + q] = obj[q];
-  if (!pred) return;
+  if (!final_outputs<FT>(p, pb, t, info, pred, obj)) return;
   // train-target mean and unbiased variance, in gps_fitc_set_data's order
   double ysum = 0.0, yss = 0.0;
   for (int i = 0; i < n; ++i) ysum += s.y[i];
@@ -540,15 +498,7 @@ __global__ __launch_bounds__(FT) void batch_fitc_kernel(BatchFitcParams p) {
       }
       if (p.yt) {
         const double yv = p.yt[pb * p.nt + row];
-        sums[0] += crps_term(mu, c, yv);
-        const double ls = logs_term(mu, c, yv);
-        sums[1] += ls;
-        const double e0 = yv - ymean;
-        sums[2] += ls - (triv_c + e0 * e0 / (2.0 * yvar));
-        sums[3] += (mu - yv) * (mu - yv);
-        sums[4] += e0 * e0;
-        const double sd = sqrt(c);
-        sums[5] += ((mu + 2.0 * sd - yv) > 0.0 && (yv - (mu - 2.0 * sd)) > 0.0) ? 1.0 : 0.0;
+        score_row_add(sums, mu, c, yv, ymean, yvar, triv_c);
       }
     }
   }
@@ -563,14 +513,7 @@ __global__ __launch_bounds__(FT) void batch_fitc_kernel(BatchFitcParams p) {
       for (int w = 0; w < FT / 64; ++w) acc += s.sh[q * 16 + w];
       tot[q] = acc;
     }
-    const double nt = (double)p.nt;
-    double* sc = p.sc + pb * GPS_N_SC;
-    sc[GPS_SC_CRPS] = tot[0] / nt;
-    sc[GPS_SC_LOGS] = tot[1] / nt;
-    sc[GPS_SC_MSLL] = tot[2] / nt;
-    sc[GPS_SC_SMSE] = tot[3] / tot[4];
-    sc[GPS_SC_MSE] = tot[3] / nt;
-    sc[GPS_SC_COVER] = tot[5] / nt;
+    scores_store(p, pb, tot);
   }
 }
 
@@ -587,23 +530,10 @@ hipError_t launch_batch_fitc(const BatchFitcParams& p, hipStream_t s) {
       p.d > GPS_BATCH_MAX_D || p.nprob < 1 || (p.n_ell != 1 && p.n_ell != p.d) || p.nsteps < 0 ||
       p.nsteps > kBatchStepsPerLaunch)
     return hipErrorInvalidValue;
-  // the dynamic-LDS limit is a per-device function attribute: set once per device under a lock
-  // (as launch_batch)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = raise_dynamic_lds(
+      (const void*)batch_fitc_kernel,
+      batch_fitc_lds_bytes(GPS_SURFACE_MAX_N, GPS_BATCH_FITC_MAX_M, GPS_BATCH_MAX_D));
   if (e != hipSuccess) return e;
-  {
-    static std::mutex mu;
-    static std::set<int> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      e = hipFuncSetAttribute(
-          (const void*)batch_fitc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)batch_fitc_lds_bytes(GPS_SURFACE_MAX_N, GPS_BATCH_FITC_MAX_M, GPS_BATCH_MAX_D));
-      if (e != hipSuccess) return e;
-      done.insert(dev);
-    }
-  }
   hipLaunchKernelGGL(batch_fitc_kernel, dim3((unsigned)p.nprob), dim3(FT),
                      batch_fitc_lds_bytes(p.n, p.m, p.d), s, p);
   return hipGetLastError();

@@ -26,9 +26,6 @@
 // launch split.  Every loop bound is a function of n, m, d, nt and nsteps; every exit is
 // workgroup-uniform (pivots are read from one LDS word by all); every shuffle is executed by all
 // lanes of its wave.  Plain FP64 FMAs.
-#include <mutex>
-#include <set>
-
 #include "batch_fitc_shared.h"
 #include "gps_internal.h"
 #include "gpscore.h"
@@ -522,7 +519,6 @@ __global__ __launch_bounds__(FT) void batch_fitc_tall_kernel(BatchFitcTallParams
   const Ws w = carve_ws(tp.ws + pb * tp.ws_stride, n, s.ld);
   const double* x = p.x + pb * n * d;
   const double* y = p.y + pb * n;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   double* il = s.th + 20;
   int info = p.info[pb];
   int done = p.steps_done[pb];
@@ -611,45 +607,14 @@ __global__ __launch_bounds__(FT) void batch_fitc_tall_kernel(BatchFitcTallParams
   __syncthreads();
 
   if (p.mode == BATCH_MODE_GRAD) {
-    if (info) {
-      if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = nan;
-      if (t < nth) p.grad[pb * nth + t] = nan;
-      for (int e = t; e < m * d; e += FT) p.grad_z[pb * m * d + e] = nan;
-    }
-    if (t == 0) p.info[pb] = info;
+    fitc_grad_end(p, pb, t, info);
     return;
   }
-  // a failed problem (in this launch or an earlier one): NaN in the rest of its series
-  if (info) {
-    const int s0 = done > p.step0 ? done : p.step0;
-    const int s1 = p.step0 + p.nsteps;
-    for (int e = s0 + t; e < s1; e += FT) p.values[pb * p.itr + e] = nan;
-    for (int64_t e = (int64_t)s0 * nth + t; e < (int64_t)s1 * nth; e += FT)
-      p.thetas[pb * p.itr * nth + e] = nan;
-  }
-  if (t < nth) p.theta[pb * nth + t] = s.th[t];
-  for (int e = t; e < m * d; e += FT) p.z[pb * m * d + e] = s.zs[e];
-  if (t == 0) {
-    p.stale[pb] = stale;
-    p.steps_done[pb] = done;
-    p.info[pb] = info;
-  }
+  train_write_back<FT>(p, pb, t, s.th, s.zs, info, done, stale);
+  if (t == 0) p.info[pb] = info;
   if (!p.do_final) return;
   const bool pred = p.xt != nullptr && p.nt > 0;
-  if (info) {
-    if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = nan;
-    if (pred) {
-      for (int e = t; e < p.nt; e += FT) {
-        p.mu[pb * p.nt + e] = nan;
-        p.var[pb * p.nt + e] = nan;
-      }
-      if (p.yt && t < GPS_N_SC) p.sc[pb * GPS_N_SC + t] = nan;
-    }
-    return;
-  }
-  if (t == 0)
-    for (int q = 0; q < GPS_N_OBJ; ++q) p.obj[pb * GPS_N_OBJ + q] = obj[q];
-  if (!pred) return;
+  if (!final_outputs<FT>(p, pb, t, info, pred, obj)) return;
   // train-target mean and unbiased variance, in gps_fitc_set_data's order
   double ysum = 0.0, yss = 0.0;
   for (int i = 0; i < n; ++i) ysum += y[i];
@@ -693,15 +658,7 @@ __global__ __launch_bounds__(FT) void batch_fitc_tall_kernel(BatchFitcTallParams
       }
       if (p.yt) {
         const double yv = p.yt[pb * p.nt + row];
-        sums[0] += crps_term(mu, c, yv);
-        const double ls = logs_term(mu, c, yv);
-        sums[1] += ls;
-        const double e0 = yv - ymean;
-        sums[2] += ls - (triv_c + e0 * e0 / (2.0 * yvar));
-        sums[3] += (mu - yv) * (mu - yv);
-        sums[4] += e0 * e0;
-        const double sd = sqrt(c);
-        sums[5] += ((mu + 2.0 * sd - yv) > 0.0 && (yv - (mu - 2.0 * sd)) > 0.0) ? 1.0 : 0.0;
+        score_row_add(sums, mu, c, yv, ymean, yvar, triv_c);
       }
     }
   }
@@ -716,14 +673,7 @@ __global__ __launch_bounds__(FT) void batch_fitc_tall_kernel(BatchFitcTallParams
       for (int w4 = 0; w4 < FT / 64; ++w4) acc += s.sh[q * 16 + w4];
       tot[q] = acc;
     }
-    const double nt = (double)p.nt;
-    double* sc = p.sc + pb * GPS_N_SC;
-    sc[GPS_SC_CRPS] = tot[0] / nt;
-    sc[GPS_SC_LOGS] = tot[1] / nt;
-    sc[GPS_SC_MSLL] = tot[2] / nt;
-    sc[GPS_SC_SMSE] = tot[3] / tot[4];
-    sc[GPS_SC_MSE] = tot[3] / nt;
-    sc[GPS_SC_COVER] = tot[5] / nt;
+    scores_store(p, pb, tot);
   }
 }
 
@@ -752,24 +702,10 @@ hipError_t launch_batch_fitc_tall(const BatchFitcTallParams& tp, hipStream_t s) 
       p.nsteps < 0 || p.nsteps > batch_fitc_tall_steps(p.n) || !tp.ws ||
       tp.ws_stride < batch_fitc_tall_ws_doubles(p.n, p.m))
     return hipErrorInvalidValue;
-  // the dynamic-LDS limit is a per-device function attribute: set once per device under a lock
-  // (as launch_batch)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = raise_dynamic_lds(
+      (const void*)batch_fitc_tall_kernel,
+      batch_fitc_tall_lds_bytes(GPS_BATCH_FITC_TALL_MAX_N, GPS_BATCH_FITC_MAX_M, GPS_BATCH_MAX_D));
   if (e != hipSuccess) return e;
-  {
-    static std::mutex mu;
-    static std::set<int> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      e = hipFuncSetAttribute(
-          (const void*)batch_fitc_tall_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)batch_fitc_tall_lds_bytes(GPS_BATCH_FITC_TALL_MAX_N, GPS_BATCH_FITC_MAX_M,
-                                         GPS_BATCH_MAX_D));
-      if (e != hipSuccess) return e;
-      done.insert(dev);
-    }
-  }
   hipLaunchKernelGGL(batch_fitc_tall_kernel, dim3((unsigned)p.nprob), dim3(FT),
                      batch_fitc_tall_lds_bytes(p.n, p.m, p.d), s, tp);
   return hipGetLastError();

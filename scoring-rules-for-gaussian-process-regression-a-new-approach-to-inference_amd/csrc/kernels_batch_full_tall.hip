@@ -31,9 +31,7 @@
 // A workspace slice is touched by its own workgroup only, __syncthreads() is all the ordering there
 // is; every sum's order is a function of n, d and the 256 threads, so results are bitwise
 // independent of the batch size, the problem's position and the launch split.
-#include <mutex>
-#include <set>
-
+#include "batch_driver.h"
 #include "gps_internal.h"
 #include "gpscore.h"
 
@@ -537,7 +535,6 @@ __global__ __launch_bounds__(BT) void batch_full_tall_kernel(BatchFullTallParams
   const int nth = 2 + p.n_ell;
   const int64_t pb = blockIdx.x;
   const Lds s = carve(sm, np);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   double* il = s.th + 20;
   const double* x = p.x + pb * n * d;
   double* W0 = tp.ws + pb * tp.ws_stride;
@@ -610,45 +607,14 @@ __global__ __launch_bounds__(BT) void batch_full_tall_kernel(BatchFullTallParams
   __syncthreads();
 
   if (p.mode == BATCH_MODE_GRAD) {
-    if (t == 0) {
-      p.info[pb] = info;
-      if (info) {
-        for (int q = 0; q < GPS_N_OBJ; ++q) p.obj[pb * GPS_N_OBJ + q] = nan;
-        for (int q = 0; q < nth; ++q) p.grad[pb * nth + q] = nan;
-      }
-    }
+    full_grad_end(p, pb, t, info);
     return;
   }
-  // a failed problem (in this launch or an earlier one): NaN in the rest of its series
-  if (info) {
-    const int s0 = done > p.step0 ? done : p.step0;
-    const int s1 = p.step0 + p.nsteps;
-    for (int e = s0 + t; e < s1; e += BT) p.values[pb * p.itr + e] = nan;
-    for (int64_t e = (int64_t)s0 * nth + t; e < (int64_t)s1 * nth; e += BT)
-      p.thetas[pb * p.itr * nth + e] = nan;
-  }
-  if (t < nth) p.theta[pb * nth + t] = s.th[t];
-  if (t == 0) {
-    p.stale[pb] = stale;
-    p.steps_done[pb] = done;
-    p.info[pb] = info;
-  }
+  train_write_back<BT>(p, pb, t, s.th, nullptr, info, done, stale);
+  if (t == 0) p.info[pb] = info;
   if (!p.do_final) return;
   const bool pred = p.xt != nullptr && p.nt > 0;
-  if (info) {
-    if (t < GPS_N_OBJ) p.obj[pb * GPS_N_OBJ + t] = nan;
-    if (pred) {
-      for (int e = t; e < p.nt; e += BT) {
-        p.mu[pb * p.nt + e] = nan;
-        p.var[pb * p.nt + e] = nan;
-      }
-      if (p.yt && t < GPS_N_SC) p.sc[pb * GPS_N_SC + t] = nan;
-    }
-    return;
-  }
-  if (t == 0)
-    for (int q = 0; q < GPS_N_OBJ; ++q) p.obj[pb * GPS_N_OBJ + q] = obj[q];
-  if (!pred) return;
+  if (!final_outputs<BT>(p, pb, t, info, pred, obj)) return;
   // train-target mean and unbiased variance, in gps_full_set_data's order
   double ysum = 0.0, yss = 0.0;
   for (int i = 0; i < n; ++i) ysum += s.y[i];
@@ -715,15 +681,7 @@ __global__ __launch_bounds__(BT) void batch_full_tall_kernel(BatchFullTallParams
       p.var[row] = cv;
       if (p.yt) {
         const double yv = p.yt[row];
-        sums[0] += crps_term(m, cv, yv);
-        const double ls = logs_term(m, cv, yv);
-        sums[1] += ls;
-        const double e0 = yv - ymean;
-        sums[2] += ls - (triv_c + e0 * e0 / (2.0 * yvar));
-        sums[3] += (m - yv) * (m - yv);
-        sums[4] += e0 * e0;
-        const double sd = sqrt(cv);
-        sums[5] += ((m + 2.0 * sd - yv) > 0.0 && (yv - (m - 2.0 * sd)) > 0.0) ? 1.0 : 0.0;
+        score_row_add(sums, m, cv, yv, ymean, yvar, triv_c);
       }
     }
     __syncthreads();
@@ -731,14 +689,7 @@ __global__ __launch_bounds__(BT) void batch_full_tall_kernel(BatchFullTallParams
   if (!p.yt) return;
   block_sum<6>(sums, s.sh);
   if (t == 0) {
-    const double nt = (double)p.nt;
-    double* sc = p.sc + pb * GPS_N_SC;
-    sc[GPS_SC_CRPS] = sums[0] / nt;
-    sc[GPS_SC_LOGS] = sums[1] / nt;
-    sc[GPS_SC_MSLL] = sums[2] / nt;
-    sc[GPS_SC_SMSE] = sums[3] / sums[4];
-    sc[GPS_SC_MSE] = sums[3] / nt;
-    sc[GPS_SC_COVER] = sums[5] / nt;
+    scores_store(p, pb, sums);
   }
 }
 
@@ -769,22 +720,9 @@ hipError_t launch_batch_full_tall(const BatchFullTallParams& tp, hipStream_t s) 
       tp.ws_stride < batch_full_tall_ws_doubles(p.n) || (tp.ws_stride & 3) ||
       (reinterpret_cast<uintptr_t>(tp.ws) & 31))
     return hipErrorInvalidValue;
-  // the dynamic-LDS limit is a per-device function attribute: set once per device under a lock
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = raise_dynamic_lds((const void*)batch_full_tall_kernel,
+                                         batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
   if (e != hipSuccess) return e;
-  {
-    static std::mutex mu;
-    static std::set<int> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      e = hipFuncSetAttribute((const void*)batch_full_tall_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
-      if (e != hipSuccess) return e;
-      done.insert(dev);
-    }
-  }
   hipLaunchKernelGGL(batch_full_tall_kernel, dim3((unsigned)p.nprob), dim3(BT),
                      batch_full_tall_lds_bytes(p.n), s, tp);
   return hipGetLastError();

@@ -15,6 +15,7 @@
 // objectives for that point (R's chol would stop the script; the grid keeps going).
 #include <mutex>
 #include <set>
+#include <utility>
 
 #include "gps_internal.h"
 
@@ -117,28 +118,30 @@ __global__ __launch_bounds__(64) void surface_kernel(SurfaceParams p) {
 
 size_t surface_lds_bytes(int n) { return (size_t)(n * (n + 1) + n) * sizeof(double); }
 
-hipError_t launch_surface(const SurfaceParams& p, hipStream_t s) {
-  if (p.n < 1 || p.n > GPS_SURFACE_MAX_N || p.d < 1 || p.nl < 1 || p.ns < 1)
-    return hipErrorInvalidValue;
-  const size_t lds = surface_lds_bytes(p.n);
-  // the dynamic-LDS limit (133 KB at n = 128) is a per-device function attribute: set once per
-  // device under a lock, so contexts on several threads or devices never race on it
+// The dynamic-LDS limit (133 KB for the surface kernel at n = 128) is a per-device function
+// attribute: raised once per (device, kernel) under a lock, so contexts on several threads or
+// devices never race on it.  `bytes` is the most the kernel is ever launched with.
+hipError_t raise_dynamic_lds(const void* kernel, size_t bytes) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  {
-    static std::mutex mu;
-    static std::set<int> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      e = hipFuncSetAttribute((const void*)surface_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)surface_lds_bytes(GPS_SURFACE_MAX_N));
-      if (e != hipSuccess) return e;
-      done.insert(dev);
-    }
-  }
-  hipLaunchKernelGGL(surface_kernel, dim3((unsigned)(p.nl * p.ns)), dim3(64), lds, s, p);
+  static std::mutex mu;
+  static std::set<std::pair<int, const void*>> done;
+  std::lock_guard<std::mutex> lk(mu);
+  if (done.count({dev, kernel})) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) done.insert({dev, kernel});
+  return e;
+}
+
+hipError_t launch_surface(const SurfaceParams& p, hipStream_t s) {
+  if (p.n < 1 || p.n > GPS_SURFACE_MAX_N || p.d < 1 || p.nl < 1 || p.ns < 1)
+    return hipErrorInvalidValue;
+  const hipError_t e =
+      raise_dynamic_lds((const void*)surface_kernel, surface_lds_bytes(GPS_SURFACE_MAX_N));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(surface_kernel, dim3((unsigned)(p.nl * p.ns)), dim3(64),
+                     surface_lds_bytes(p.n), s, p);
   return hipGetLastError();
 }
 
