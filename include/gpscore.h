@@ -592,6 +592,36 @@ int gps_full_train_tall(gps_ctx* ctx, int kind, int objective, int64_t nprob, co
                         int flags, double* theta_out, double* values, double* thetas, double* obj,
                         double* mu, double* var, double* sc, int* info, int* steps_done);
 
+/* ---- batches of full GPs of up to 512 rows on the block-LOO objectives ----------
+ * gps_full_grad_tall / gps_full_train_tall with the objective GPS_BLOCK_DSS or GPS_BLOCK_KC over
+ * nfold folds [int(f·n/nfold), int((f+1)·n/nfold)) (gps_full_blockloo's objectives and folds: the
+ * 4-fold DSS fit of "kin40k-FULL-compare.py", KF:487-601, 150 steps at lr 1e-3, and its CRPS
+ * sibling K20:655-720) for a whole batch: the same model, limits (1 <= n <= 512, d <= 16, n_ell =
+ * 1 or d, GPS_ARD or GPS_RBF), SGD loop, final pass, outputs (which may be NULL included),
+ * GPS_BATCH_STALE_NOISE, failure semantics and bitwise independence of nprob, position and launch
+ * split.  2 <= nfold <= 32 and nfold <= n; GPS_BLOCK_ES is refused (it needs draws and a matrix
+ * square root: gps_full_blockloo_es).  The value + gradient call returns value[q], the objective
+ * of problem q, fold_values[q·nfold + f], fold f's term of it (may be NULL), obj, the five
+ * GPS_OBJ_* entries at θ (may be NULL), and grad as gps_full_grad_tall; the training call's
+ * values[q·itr + i] is the block objective before step i.  info[q] is 0, k in 1..n (the leading
+ * minor of order k of A = K + σ²I is not positive definite, as everywhere) or n + k: the pivot of
+ * global row k (1-based) of its fold's block P_f = (A⁻¹)_ff is not > 0 — an internal error, since a
+ * positive definite A has positive definite P_f; the problem's outputs are NaN either way.  One
+ * workgroup per problem; the per-problem workspace is np² + max(np², 2·bp²) + np² doubles (np =
+ * 64·ceil(n/64), bp = 64·ceil(ceil(n/nfold)/64)), and a batch whose inputs, outputs or workspace
+ * exceed 8 GiB is refused; a launch runs min(64, max(1, 1024 / ceil(n/64)³)) steps.  They agree
+ * with gps_full_blockloo within rounding, never bitwise. */
+int gps_full_blockloo_grad_tall(gps_ctx* ctx, int kind, int objective, int nfold, int64_t nprob,
+                                const double* X, const double* y, int64_t n, int d,
+                                const double* theta, int n_ell, double* value,
+                                double* fold_values, double* obj, double* grad, int* info);
+int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfold, int64_t nprob,
+                                 const double* X, const double* y, int64_t n, int d,
+                                 const double* theta0, int n_ell, int64_t itr, double lr,
+                                 const double* Xt, const double* yt, int64_t nt, int flags,
+                                 double* theta_out, double* values, double* thetas, double* obj,
+                                 double* mu, double* var, double* sc, int* info, int* steps_done);
+
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */
 int gps_comm_unique_id(char uid[128]);
 int gps_comm_init(gps_ctx* ctx, int nranks, int rank, const char uid[128]);

@@ -1,8 +1,10 @@
-// C-ABI, the four "one workgroup per problem" batch paths:
+// C-ABI, the five "one workgroup per problem" batch paths:
 //   gps_full_{grad,train}_batch  small full GPs, n <= 128            kernels_batch.hip
 //   gps_fitc_{grad,train}_batch  small FITC GPs, n <= 128, m <= 32   kernels_batch_fitc.hip
 //   gps_fitc_{grad,train}_tall   FITC GPs, n <= 2048                 kernels_batch_fitc_tall.hip
 //   gps_full_{grad,train}_tall   full GPs, n <= 512                  kernels_batch_full_tall.hip
+//   gps_full_blockloo_{grad,train}_tall  the same on the block-LOO DSS / KC objectives
+//                                                                    kernels_batch_full_tall_block.hip
 // value + gradient of every problem at its own θ (and Z), and the SGD fit loops of the scripts'
 // replicate loops for a whole batch with the final predictive and score bundle.  The calls own
 // their device buffers:
@@ -11,12 +13,13 @@
 //            per-problem workspace; the full-tall path pads the head to a multiple of 8 doubles
 //            (its workspace is read in 16-byte pieces)
 //   btint    info | steps_done
-//   btout    GRAD: obj | grad | grad_z;  TRAIN: values | thetas | obj | mu | var | sc
+//   btout    GRAD: obj | grad | grad_z | value | fold_values (the last two: block-LOO);
+//            TRAIN: values | thetas | obj | mu | var | sc
 // Every call uploads all it reads, so nothing is carried from one batch call to the next; the
 // resident full-GP / FITC data, any fit and the test buffers are not touched, and nothing is
 // sharded, so a communicator does not matter.  A path is one Path constant: its limit on n, its
-// workspace, its steps-per-launch rule, its launcher and its profiling tags; everything else is
-// the two routines grad_call and train_call.
+// objective rule, its workspace, its steps-per-launch rule, its launcher and its profiling tags;
+// everything else is the two routines grad_call and train_call.
 #include <type_traits>
 
 #include "api_internal.h"
@@ -29,40 +32,65 @@ const char* const kTooBig = "batch: more than 8 GiB of inputs or outputs, split 
 template <class P>
 constexpr bool kFitc = std::is_same<P, BatchFitcParams>::value;
 
+// what only the block-LOO path has: the fold count and BATCH_MODE_GRAD's two extra outputs
+struct Block {
+  int nfold;
+  double *value, *fold_values;
+};
+
 template <class P>
 struct Path {
   int64_t max_n;
   const char* n_msg;
   const char *grad_tag, *train_tag;
-  int64_t (*ws)(int64_t n, int m);  // workspace doubles per problem behind the state, or NULL
+  // workspace doubles per problem behind the state, or NULL
+  int64_t (*ws)(int64_t n, int m, int nfold);
   bool pad;                         // the state's head is padded to a multiple of 8 doubles
   int (*steps)(int64_t n);          // SGD steps one launch may run
-  hipError_t (*launch)(const P& p, double* ws, int64_t ws_stride, hipStream_t s);
+  hipError_t (*launch)(const P& p, double* ws, int64_t ws_stride, const Block& b, hipStream_t s);
+  bool block;                       // the objective is a GPS_BLOCK_* code over nfold folds
 };
 
 const Path<BatchParams> kFull = {
     GPS_SURFACE_MAX_N, "batch: n must be in 1..128", "batch_grad", "batch_train", nullptr, false,
     [](int64_t) { return kBatchStepsPerLaunch; },
-    [](const BatchParams& p, double*, int64_t, hipStream_t s) { return launch_batch(p, s); }};
+    [](const BatchParams& p, double*, int64_t, const Block&, hipStream_t s) {
+      return launch_batch(p, s);
+    },
+    false};
 const Path<BatchFitcParams> kFitcSmall = {
     GPS_SURFACE_MAX_N, "batch: n must be in 1..128", "batch_fitc_grad", "batch_fitc_train", nullptr,
     false, [](int64_t) { return kBatchStepsPerLaunch; },
-    [](const BatchFitcParams& p, double*, int64_t, hipStream_t s) {
+    [](const BatchFitcParams& p, double*, int64_t, const Block&, hipStream_t s) {
       return launch_batch_fitc(p, s);
-    }};
+    },
+    false};
 const Path<BatchFitcParams> kFitcTall = {
     GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_grad",
-    "batch_fitc_tall_train", batch_fitc_tall_ws_doubles, false, batch_fitc_tall_steps,
-    [](const BatchFitcParams& p, double* ws, int64_t stride, hipStream_t s) {
+    "batch_fitc_tall_train", [](int64_t n, int m, int) { return batch_fitc_tall_ws_doubles(n, m); },
+    false, batch_fitc_tall_steps,
+    [](const BatchFitcParams& p, double* ws, int64_t stride, const Block&, hipStream_t s) {
       return launch_batch_fitc_tall(BatchFitcTallParams{p, ws, stride}, s);
-    }};
+    },
+    false};
 const Path<BatchParams> kFullTall = {
     GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_grad",
-    "batch_full_tall_train", [](int64_t n, int) { return batch_full_tall_ws_doubles(n); }, true,
-    batch_full_tall_steps,
-    [](const BatchParams& p, double* ws, int64_t stride, hipStream_t s) {
+    "batch_full_tall_train", [](int64_t n, int, int) { return batch_full_tall_ws_doubles(n); },
+    true, batch_full_tall_steps,
+    [](const BatchParams& p, double* ws, int64_t stride, const Block&, hipStream_t s) {
       return launch_batch_full_tall(BatchFullTallParams{p, ws, stride}, s);
-    }};
+    },
+    false};
+const Path<BatchParams> kFullTallBlock = {
+    GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_block_grad",
+    "batch_full_tall_block_train",
+    [](int64_t n, int, int nfold) { return batch_full_tall_block_ws_doubles(n, nfold); }, true,
+    batch_full_tall_block_steps,
+    [](const BatchParams& p, double* ws, int64_t stride, const Block& b, hipStream_t s) {
+      return launch_batch_full_tall_block(
+          BatchFullTallBlockParams{p, ws, stride, b.nfold, 0, b.value, b.fold_values}, s);
+    },
+    true};
 
 // what every entry is given; Z and m are NULL and 0, and kind is unused, where the entry has none
 struct Problem {
@@ -75,17 +103,25 @@ struct Problem {
   int m;
   const double* theta;
   int n_ell;
+  int nfold = 0;  // the block-LOO path's fold count
 };
 
 template <class P>
 int check_problem(gps_ctx* ctx, const Path<P>& path, const Problem& a) {
   ARGCHK(a.X && a.y && (!kFitc<P> || a.Z) && a.theta, "NULL argument");
   if (!kFitc<P>) ARGCHK(a.kind == GPS_ARD || a.kind == GPS_RBF, "kind must be GPS_ARD or GPS_RBF");
-  ARGCHK(a.objective == GPS_OBJ_NLML || a.objective == GPS_OBJ_LOO_CRPS ||
-             a.objective == GPS_OBJ_LOO_LOGS,
-         "objective must be GPS_OBJ_NLML, GPS_OBJ_LOO_CRPS or GPS_OBJ_LOO_LOGS");
+  if (path.block)
+    ARGCHK(a.objective == GPS_BLOCK_DSS || a.objective == GPS_BLOCK_KC,
+           "objective must be GPS_BLOCK_DSS or GPS_BLOCK_KC");
+  else
+    ARGCHK(a.objective == GPS_OBJ_NLML || a.objective == GPS_OBJ_LOO_CRPS ||
+               a.objective == GPS_OBJ_LOO_LOGS,
+           "objective must be GPS_OBJ_NLML, GPS_OBJ_LOO_CRPS or GPS_OBJ_LOO_LOGS");
   ARGCHK(a.nprob >= 1 && a.nprob <= (1 << 20), "batch: nprob must be in 1..2^20");
   ARGCHK(a.n >= 1 && a.n <= path.max_n, path.n_msg);
+  if (path.block)
+    ARGCHK(a.nfold >= 2 && a.nfold <= GPS_BATCH_BLOCK_MAX_FOLDS && a.nfold <= a.n,
+           "batch: nfold must be in 2..32 and at most n");
   if (kFitc<P>) ARGCHK(a.m >= 1 && a.m <= GPS_BATCH_FITC_MAX_M, "batch: m must be in 1..32");
   ARGCHK(a.d >= 1 && a.d <= GPS_BATCH_MAX_D, "batch: d must be in 1..16");
   ARGCHK(a.n_ell == 1 || a.n_ell == a.d, "n_ell must be 1 or d");
@@ -159,25 +195,36 @@ int download(gps_ctx* ctx, T* dst, const T* src, int64_t count) {
 
 template <class P>
 int grad_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, double* obj, double* grad,
-              double* grad_z, int* info) {
+              double* grad_z, int* info, double* value = nullptr, double* fold_values = nullptr) {
   if (int rc = bind(ctx)) return rc;
   if (int rc = check_problem(ctx, path, a)) return rc;
-  ARGCHK(grad && (!kFitc<P> || grad_z) && info, "NULL argument");
+  ARGCHK(grad && (!kFitc<P> || grad_z) && info && (!path.block || value), "NULL argument");
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
-  const int64_t stride = path.ws ? path.ws(a.n, a.m) : 0, n_ws = nprob * stride;
+  const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold) : 0, n_ws = nprob * stride;
+  const int64_t n_blk = path.block ? nprob * (1 + a.nfold) : 0;
   if (path.ws)  // the small paths' value + gradient calls have no such guard
     ARGCHK(nprob * a.n * (a.d + 1) + nprob * nz <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
   P p;
   double* ws;
-  if (int rc = carve(ctx, path, a, 0, nprob * (GPS_N_OBJ + nth + nz), n_ws, p, &ws)) return rc;
+  if (int rc = carve(ctx, path, a, 0, nprob * (GPS_N_OBJ + nth + nz) + n_blk, n_ws, p, &ws))
+    return rc;
   p.mode = BATCH_MODE_GRAD;
   p.obj = ctx->btout.d();
   p.grad = p.obj + nprob * GPS_N_OBJ;
   if constexpr (kFitc<P>) p.grad_z = p.grad + nprob * nth;
+  Block blk = {a.nfold, nullptr, nullptr};
+  if (path.block) {
+    blk.value = p.grad + nprob * (nth + nz);
+    blk.fold_values = blk.value + nprob;
+  }
   if (int rc = upload(ctx, a, p, nullptr, nullptr, nullptr)) return rc;
   {
     Prof pr(ctx, path.grad_tag, 0, 0);
-    HIPCHK(path.launch(p, ws, stride, ctx->stream));
+    HIPCHK(path.launch(p, ws, stride, blk, ctx->stream));
+  }
+  if (path.block) {
+    if (int rc = download(ctx, value, blk.value, nprob)) return rc;
+    if (int rc = download(ctx, fold_values, blk.fold_values, nprob * a.nfold)) return rc;
   }
   if (int rc = download(ctx, obj, p.obj, nprob * GPS_N_OBJ)) return rc;
   if (int rc = download(ctx, grad, p.grad, nprob * nth)) return rc;
@@ -207,7 +254,7 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
   const int64_t n_in = nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + nprob * nz;
   const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC);
-  const int64_t stride = path.ws ? path.ws(a.n, a.m) : 0, n_ws = nprob * stride;
+  const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold) : 0, n_ws = nprob * stride;
   ARGCHK(n_in <= kMaxDoubles && n_out <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
   P p;
   double* ws;
@@ -241,7 +288,7 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
       p.step0 = (int)step;
       p.nsteps = (int)ns;
       p.do_final = step + ns == itr;
-      HIPCHK(path.launch(p, ws, stride, ctx->stream));
+      HIPCHK(path.launch(p, ws, stride, Block{a.nfold, nullptr, nullptr}, ctx->stream));
       step += ns;
     } while (step < itr);
   }
@@ -296,6 +343,27 @@ int gps_full_train_tall(gps_ctx* ctx, int kind, int objective, int64_t nprob, co
   return train_call(ctx, kFullTall, {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell},
                     itr, lr, 0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu,
                     var, sc, info, steps_done);
+}
+
+int gps_full_blockloo_grad_tall(gps_ctx* ctx, int kind, int objective, int nfold, int64_t nprob,
+                                const double* X, const double* y, int64_t n, int d,
+                                const double* theta, int n_ell, double* value,
+                                double* fold_values, double* obj, double* grad, int* info) {
+  return grad_call(ctx, kFullTallBlock,
+                   {kind, objective, nprob, X, y, n, d, nullptr, 0, theta, n_ell, nfold}, obj, grad,
+                   nullptr, info, value, fold_values);
+}
+
+int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfold, int64_t nprob,
+                                 const double* X, const double* y, int64_t n, int d,
+                                 const double* theta0, int n_ell, int64_t itr, double lr,
+                                 const double* Xt, const double* yt, int64_t nt, int flags,
+                                 double* theta_out, double* values, double* thetas, double* obj,
+                                 double* mu, double* var, double* sc, int* info, int* steps_done) {
+  return train_call(ctx, kFullTallBlock,
+                    {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell, nfold}, itr, lr,
+                    0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu, var, sc,
+                    info, steps_done);
 }
 
 int gps_fitc_grad_batch(gps_ctx* ctx, int objective, int64_t nprob, const double* X,

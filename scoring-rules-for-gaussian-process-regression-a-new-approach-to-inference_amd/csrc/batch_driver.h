@@ -1,5 +1,6 @@
-// The step driver the four "one workgroup per problem" batch kernels share (kernels_batch.hip,
-// kernels_batch_fitc.hip, kernels_batch_fitc_tall.hip, kernels_batch_full_tall.hip):
+// The step driver the "one workgroup per problem" batch kernels share (kernels_batch.hip,
+// kernels_batch_fitc.hip, kernels_batch_fitc_tall.hip, and through batch_full_tall_shared.h
+// kernels_batch_full_tall.hip and kernels_batch_full_tall_block.hip):
 // what a __global__ function there does around its own forward(), gradient() and test-row loop.
 // The helpers take the params struct P (BatchParams or BatchFitcParams) BY VALUE, the thread
 // index and raw pointers (th: θ in LDS, il = th + 20: 1/ℓ_k), the block size NT as a template

@@ -359,6 +359,28 @@ int64_t batch_full_tall_ws_doubles(int64_t n);
 int batch_full_tall_steps(int64_t n);
 hipError_t launch_batch_full_tall(const BatchFullTallParams& p, hipStream_t s);
 
+// the same batches on the block-LOO objectives GPS_BLOCK_DSS / GPS_BLOCK_KC over nfold folds
+// (kernels_batch_full_tall_block.hip): b.objective is the GPS_BLOCK_* code, everything
+// else in b means what it means above.  info is 0, k in 1..n (A's leading minor k failed) or n + k
+// (the pivot of global row k of its fold's P_f = (A⁻¹)_ff is not > 0: an internal error, a positive
+// definite A has positive definite P_f).
+#define GPS_BATCH_BLOCK_MAX_FOLDS 32
+struct BatchFullTallBlockParams {
+  BatchParams b;
+  double* ws;           // [nprob][ws_stride]: W0 (np²) | W1 (max(np², 2·bp²)) | W2 (np²), np and bp
+                        // the padded n and largest fold; 32-byte aligned
+  int64_t ws_stride;    // >= batch_full_tall_block_ws_doubles(n, nfold), a multiple of 4
+  int nfold;            // 2..GPS_BATCH_BLOCK_MAX_FOLDS, <= n
+  int64_t w1;           // W1's doubles, set by the launcher
+  double* value;        // [nprob] BATCH_MODE_GRAD: the block objective
+  double* fold_values;  // [nprob][nfold] BATCH_MODE_GRAD: each fold's term, or NULL
+};
+size_t batch_full_tall_block_lds_bytes(int n);  // batch_full_tall_lds_bytes(n): no new LDS
+int64_t batch_full_tall_block_ws_doubles(int64_t n, int nfold);
+// SGD steps one launch may run, batch_full_tall_steps' rule: a function of n alone
+int batch_full_tall_block_steps(int64_t n);
+hipError_t launch_batch_full_tall_block(const BatchFullTallBlockParams& p, hipStream_t s);
+
 // ------------------------------------------------------------------ launchers
 // raises `kernel`'s dynamic-LDS limit to `bytes` on the current device, once per (device, kernel)
 // (kernels_surface.hip); every launcher of a kernel that may need more than 64 KB calls it first

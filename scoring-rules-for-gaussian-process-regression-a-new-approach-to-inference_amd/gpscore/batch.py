@@ -1,5 +1,6 @@
 """Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
-(DESIGN §19, §20), and their siblings for taller problems (§22, §24).
+(DESIGN §19, §20), and their siblings for taller problems (§22, §24; the block-LOO DSS / KC
+objectives §26).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
@@ -7,6 +8,7 @@
     res = gpscore.fitc_train_batch(X, y, Z0, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, lr_z=1.0,
                                    itr=1000, Xt=Xt, yt=yt)
     res = gpscore.train_tall(X, y, theta0, "loo_crps", lr=1.0, itr=400, Xt=Xt, yt=yt)  # n <= 512
+    res = gpscore.blockloo_train_tall(X, y, theta0, "dss", nfold=4, lr=1e-3, itr=150, Xt=Xt, yt=yt)
 
 The replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120, three SGD
 fits each: SD:192-231, 277-301, 372-396) and contour-plot.R's n = 20 problems are many tiny,
@@ -223,6 +225,82 @@ def train_tall(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=
     arguments, refusals and BatchTrainResult."""
     return _full_train("gps_full_train_tall", BATCH_FULL_TALL_MAX_N, X, y, theta0, objective, lr,
                        itr, Xt, yt, rbf, stale_noise, ctx)
+
+
+BLOCK_BATCH_OBJS = ["dss", "kc"]  # GPS_BLOCK_DSS, GPS_BLOCK_KC
+BATCH_BLOCK_MAX_FOLDS = 32        # GPS_BATCH_BLOCK_MAX_FOLDS
+
+
+def _block_objective(objective):
+    if objective not in BLOCK_BATCH_OBJS:
+        raise ValueError(f"objective must be one of {BLOCK_BATCH_OBJS} (the pointwise objectives go "
+                         f"through train_tall, the energy score through GP.block_loo), got "
+                         f"{objective!r}")
+    return BLOCK_BATCH_OBJS.index(objective)
+
+
+def _nfold(nfold, n):
+    hi = min(n, BATCH_BLOCK_MAX_FOLDS)
+    if isinstance(nfold, bool) or int(nfold) != nfold or not 2 <= nfold <= hi:
+        raise ValueError(f"nfold = {nfold!r}: a batched block-LOO problem of n = {n} rows has "
+                         f"2..{hi} folds")
+    return int(nfold)
+
+
+def blockloo_value_and_grad_tall(X, y, theta, objective="dss", nfold=4, rbf=False, ctx=None):
+    """Block-LOO objective ("dss" or "kc", GP.block_loo's, over the scripts' nfold folds
+    [int(f·n/nfold), int((f+1)·n/nfold))) and its analytic gradient for B full GPs of 1 <= n <=
+    512 training points at their own θ (one gps_full_blockloo_grad_tall call).
+    Arguments, refusals and ``info`` as value_and_grad_tall; ``info`` n + k reports an internal
+    error at global row k of its fold's block.  Returns (values (B,), grads (B, 2 + n_ell),
+    fold_values (B, nfold), objectives {name: (B,)}, info (B,))."""
+    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
+    B, n, d = X.shape
+    th, n_ell = _thetas(theta, B, d)
+    code = _block_objective(objective)
+    nfold = _nfold(nfold, n)
+    ctx = ctx or _lib.default_context()
+    vals, fold = np.empty(B), np.empty((B, nfold))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    grad = np.empty((B, 2 + n_ell))
+    info = np.zeros(B, np.int32)
+    ctx.call("gps_full_blockloo_grad_tall", GPS_RBF if rbf else GPS_ARD, code, nfold, B, ptr(X),
+             ptr(y), n, d, ptr(th), n_ell, ptr(vals), ptr(fold), ptr(obj), ptr(grad), _iptr(info))
+    return vals, grad, fold, {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, info
+
+
+def blockloo_train_tall(X, y, theta0, objective="dss", nfold=4, lr=1e-3, itr=150, Xt=None, yt=None,
+                        rbf=False, stale_noise=False, ctx=None):
+    """train_tall on a block-LOO objective (one gps_full_blockloo_train_tall call): the 4-fold DSS
+    fit of "kin40k-FULL-compare.py" (KF:487-601: 150 steps at lr 1e-3, the defaults here) or its
+    CRPS sibling "kc" (K20:655-720) for B problems at once.  ``series["objective"]`` is the block
+    objective before each step; everything else as train_tall: arguments, refusals and
+    BatchTrainResult."""
+    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
+    B, n, d = X.shape
+    th0, n_ell = _thetas(theta0, B, d)
+    code = _block_objective(objective)
+    nfold = _nfold(nfold, n)
+    itr, lr = _steps(itr, lr)
+    Xt, yt, nt = _tests(Xt, yt, B, d)
+    ctx = ctx or _lib.default_context()
+    nth = 2 + n_ell
+    theta = np.empty((B, nth))
+    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    mu = np.empty((B, nt)) if nt else None
+    var = np.empty((B, nt)) if nt else None
+    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
+    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    ctx.call("gps_full_blockloo_train_tall", GPS_RBF if rbf else GPS_ARD, code, nfold, B, ptr(X),
+             ptr(y), n, d, ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
+             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(values), ptr(thetas),
+             ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
+    return BatchTrainResult(
+        theta=theta, series={"objective": values, "theta": thetas},
+        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
+        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
+        info=info, steps_done=steps)
 
 
 def _inducing(Z, B, d):

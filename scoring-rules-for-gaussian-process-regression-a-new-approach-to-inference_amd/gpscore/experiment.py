@@ -17,7 +17,9 @@ that are trained too (SF:189-237, 301-343, 420-463): run_simple_fitc, one fitc_t
 per method.  K20's own LOO-CRPS / NLML / LOO-LogS fits (n = 500, m = 20) go the same way through
 run_fitc_batch, one fitc_train_tall call per method; its DSS and KC fits stay with run.  KF's
 LOO-CRPS / NLML / LOO-LogS fits (full GP, n = 500) have a batch route as well: run_full_batch, one
-train_tall call per method for all replicates; its block-LOO DSS and ES fits stay with run.
+train_tall call per method for all replicates; its block-LOO DSS fit goes through
+run_full_blockloo_batch, one blockloo_train_tall call for all replicates, and only its ES fit
+stays with run.
 
 Every number here comes from gpscore.GP (libgpscore.so): the SGD loops are GP.train, the
 predictive and its scores GP.predict (run_simple: gpscore.batch.train_batch).  The workbook is not shipped (the scripts open it from
@@ -33,7 +35,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
-from .batch import fitc_train_batch, fitc_train_tall, train_batch, train_tall
+from .batch import (BLOCK_BATCH_OBJS, blockloo_train_tall, fitc_train_batch, fitc_train_tall,
+                    train_batch, train_tall)
 from .gp import GP
 
 SHEETS = ("trainx", "trainy", "testx", "testy")
@@ -377,7 +380,8 @@ def run_full_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True
     array(TT, 2 + n_ell)}}: every method's TT full-GP fits (n = 500, the test predictive and the
     score bundle) are ONE train_tall call, one workgroup per replicate.  ``methods``
     defaults to the crps / nlml / logs entries of KF_METHODS; a method whose objective is dss or es
-    (block-LOO) has no batched path and raises ValueError (use run(kind="full")).  Data replicates
+    (block-LOO) raises ValueError here (dss and kc: run_full_blockloo_batch; es: run(kind="full")).
+    Data replicates
     and starting points are drawn in run's order — replicate-major, then method, initial_theta per
     method — so with the same ``seed``, ``reseed=True`` and the same method subset
     run(kind="full", methods=subset) and this fit the same problems.  ``itr`` overrides the
@@ -419,6 +423,61 @@ def run_full_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True
             raise NotPositiveDefinite(int(res.info[q]), f"run_full_batch: method {name!r}, "
                                       f"replicate {q}: the leading minor of order "
                                       f"{int(res.info[q])} is not positive definite after "
+                                      f"{int(res.steps_done[q])} steps")
+        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
+        out[name]["theta"] = res.theta.copy()
+    return out
+
+
+def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
+                            stale_noise=True, ctx=None, nfold=4):
+    """run_full_batch for KF's block-LOO fits → the same {method: {metric: array(TT), "theta":
+    array(TT, 2 + n_ell)}}: every method's TT full-GP fits on the nfold-fold block-LOO DSS (or KC)
+    objective, the test predictive and the score bundle are ONE blockloo_train_tall call, one
+    workgroup per replicate.  ``methods`` defaults to KF_METHODS' dss entry (KF:487-601,
+    150 steps at lr 1e-3); a method whose objective is es raises ValueError (use run(kind="full")),
+    one whose objective is pointwise raises too (use run_full_batch).  Data replicates and starting
+    points are drawn in run's order — replicate-major, then method, initial_theta per method — so
+    with the same ``seed``, ``reseed=True`` and the same method subset run(kind="full",
+    methods=subset) and this fit the same problems.  ``itr`` overrides the methods' step counts;
+    stale_noise as run_method.  A replicate whose factorisation fails raises
+    NotPositiveDefinite."""
+    if methods is None:
+        methods = {"dss": KF_METHODS["dss"]}
+    for name, meth in methods.items():
+        if meth.objective not in BLOCK_BATCH_OBJS:
+            route = "run(kind=\"full\")" if meth.objective == "es" else "run_full_batch"
+            raise ValueError(f"run_full_blockloo_batch: method {name!r} has objective "
+                             f"{meth.objective!r}, not one of {BLOCK_BATCH_OBJS}; use {route} for it")
+    if int(TT) != TT or TT < 1:
+        raise ValueError(f"TT must be a positive integer, got {TT!r}")
+    TT = int(TT)
+    rng = np.random.default_rng(seed)
+    rs = None if reseed else random.Random()
+    n_pool = sheets["trainx"].shape[0]
+    data, th0 = [], {name: [] for name in methods}
+    for j in range(TT):
+        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
+        data.append(dd)
+        d = dd["train_x"].shape[1]
+        for name, meth in methods.items():
+            k, ell, noise = initial_theta(meth, d, rng)
+            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
+    X = np.stack([dd["train_x"] for dd in data])
+    y = np.stack([dd["train_y"] for dd in data])
+    Xt = np.stack([dd["test_x"] for dd in data])
+    yt = np.stack([dd["test_y"] for dd in data])
+    out = {}
+    for name, meth in methods.items():
+        res = blockloo_train_tall(X, y, np.stack(th0[name]), meth.objective, nfold=nfold,
+                                  lr=meth.lr, itr=meth.itr if itr is None else int(itr), Xt=Xt,
+                                  yt=yt, stale_noise=stale_noise, ctx=ctx)
+        bad = np.flatnonzero(res.info)
+        if bad.size:
+            q = int(bad[0])
+            raise NotPositiveDefinite(int(res.info[q]), f"run_full_blockloo_batch: method {name!r}, "
+                                      f"replicate {q}: info {int(res.info[q])} (the failing "
+                                      f"leading minor, or n + the fold block's row) after "
                                       f"{int(res.steps_done[q])} steps")
         out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
         out[name]["theta"] = res.theta.copy()
