@@ -61,7 +61,9 @@ enum {
  * they are purely additive, no existing entry point or array changed; so did gps_potrf_diag
  * (DESIGN §21), gps_fitc_grad_tall / gps_fitc_train_tall, the gradient-layer
  * diagnostics gps_grad_terms_diag / gps_grad_contract_diag / gps_fitc_contract_diag
- * and gps_full_grad_tall / gps_full_train_tall.
+ * and gps_full_grad_tall / gps_full_train_tall, their block-LOO siblings
+ * gps_full_blockloo_grad_tall / gps_full_blockloo_train_tall and
+ * gps_fitc_blockloo_grad_tall / gps_fitc_blockloo_train_tall.
  * The binding refuses a mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -620,6 +622,37 @@ int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfol
                                  const double* theta0, int n_ell, int64_t itr, double lr,
                                  const double* Xt, const double* yt, int64_t nt, int flags,
                                  double* theta_out, double* values, double* thetas, double* obj,
+                                 double* mu, double* var, double* sc, int* info, int* steps_done);
+
+/* ---- batches of tall FITC GPs on the block-LOO objectives ----------------------
+ * gps_fitc_grad_tall / gps_fitc_train_tall with the objective GPS_BLOCK_DSS or GPS_BLOCK_KC over
+ * nfold folds [int(f·n/nfold), int((f+1)·n/nfold)) (gps_fitc_blockloo's objectives and folds: the
+ * 4-fold DSS and KC fits of "KIN40K-COMPARE-ALL-FITC-20", K20:523-593 and K20:655-726, 3000 steps
+ * each) for a whole batch: the same model, limits (1 <= n <= 2048, m <= 32, d <= 16, n_ell = 1 or
+ * d, ARD, jitter 1e-3), SGD loop on θ and Z, final pass, outputs, GPS_BATCH_STALE_NOISE, failure
+ * semantics and bitwise independence of nprob, position and launch split.  2 <= nfold <= 32 and
+ * nfold <= n; GPS_BLOCK_ES is refused (it needs draws and a matrix square root, and FITC has no
+ * energy-score path).  The value + gradient call returns value[q], the objective of problem q,
+ * fold_values[q·nfold + f], fold f's term of it (may be NULL), obj, the five GPS_OBJ_* entries at
+ * (θ, Z) (may be NULL), and grad / grad_z as gps_fitc_grad_tall; the training call's
+ * values[q·itr + i] is the block objective before step i.  info[q] is 0, k in 1..m or m + k as
+ * gps_fitc_grad_tall, or (2 + f)·m + k: the leading minor of order k of fold f's B₋f = K(Z,Z) +
+ * 1e-3·I + Σ_{g≠f} K_gᵀΛ_g⁻¹K_g is not > 0 — an internal error, since B₋f is K̃mm plus positive
+ * semidefinite terms; the problem's outputs are NaN either way.  One workgroup per problem; the
+ * per-problem workspace is 4n(m|1) + (nfold + 1)·m(m|1) + 11n doubles, and a batch whose inputs,
+ * outputs or workspace exceed 8 GiB is refused; a launch runs max(1, 32 / ceil(n / 128)) steps.
+ * They agree with gps_fitc_blockloo within rounding, never bitwise. */
+int gps_fitc_blockloo_grad_tall(gps_ctx* ctx, int objective, int nfold, int64_t nprob,
+                                const double* X, const double* y, int64_t n, int d,
+                                const double* Z, int m, const double* theta, int n_ell,
+                                double* value, double* fold_values, double* obj, double* grad,
+                                double* grad_z, int* info);
+int gps_fitc_blockloo_train_tall(gps_ctx* ctx, int objective, int nfold, int64_t nprob,
+                                 const double* X, const double* y, int64_t n, int d,
+                                 const double* Z0, int m, const double* theta0, int n_ell,
+                                 int64_t itr, double lr, double lr_z, const double* Xt,
+                                 const double* yt, int64_t nt, int flags, double* theta_out,
+                                 double* z_out, double* values, double* thetas, double* obj,
                                  double* mu, double* var, double* sc, int* info, int* steps_done);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */

@@ -1,10 +1,13 @@
-// C-ABI, the five "one workgroup per problem" batch paths:
+// C-ABI, the six "one workgroup per problem" batch paths (DESIGN §19, §20, §22, §24, §25, §26,
+// §27):
 //   gps_full_{grad,train}_batch  small full GPs, n <= 128            kernels_batch.hip
 //   gps_fitc_{grad,train}_batch  small FITC GPs, n <= 128, m <= 32   kernels_batch_fitc.hip
 //   gps_fitc_{grad,train}_tall   FITC GPs, n <= 2048                 kernels_batch_fitc_tall.hip
 //   gps_full_{grad,train}_tall   full GPs, n <= 512                  kernels_batch_full_tall.hip
 //   gps_full_blockloo_{grad,train}_tall  the same on the block-LOO DSS / KC objectives
 //                                                                    kernels_batch_full_tall_block.hip
+//   gps_fitc_blockloo_{grad,train}_tall  the tall FITC GPs on the block-LOO DSS / KC objectives
+//                                                                    kernels_batch_fitc_tall_block.hip
 // value + gradient of every problem at its own θ (and Z), and the SGD fit loops of the scripts'
 // replicate loops for a whole batch with the final predictive and score bundle.  The calls own
 // their device buffers:
@@ -89,6 +92,16 @@ const Path<BatchParams> kFullTallBlock = {
     [](const BatchParams& p, double* ws, int64_t stride, const Block& b, hipStream_t s) {
       return launch_batch_full_tall_block(
           BatchFullTallBlockParams{p, ws, stride, b.nfold, 0, b.value, b.fold_values}, s);
+    },
+    true};
+const Path<BatchFitcParams> kFitcTallBlock = {
+    GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_block_grad",
+    "batch_fitc_tall_block_train",
+    [](int64_t n, int m, int nfold) { return batch_fitc_tall_block_ws_doubles(n, m, nfold); },
+    false, batch_fitc_tall_block_steps,
+    [](const BatchFitcParams& p, double* ws, int64_t stride, const Block& b, hipStream_t s) {
+      return launch_batch_fitc_tall_block(
+          BatchFitcTallBlockParams{p, ws, stride, b.nfold, b.value, b.fold_values}, s);
     },
     true};
 
@@ -404,6 +417,29 @@ int gps_fitc_train_tall(gps_ctx* ctx, int objective, int64_t nprob, const double
   return train_call(ctx, kFitcTall, {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell}, itr,
                     lr, lr_z, Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc,
                     info, steps_done);
+}
+
+int gps_fitc_blockloo_grad_tall(gps_ctx* ctx, int objective, int nfold, int64_t nprob,
+                                const double* X, const double* y, int64_t n, int d,
+                                const double* Z, int m, const double* theta, int n_ell,
+                                double* value, double* fold_values, double* obj, double* grad,
+                                double* grad_z, int* info) {
+  return grad_call(ctx, kFitcTallBlock,
+                   {0, objective, nprob, X, y, n, d, Z, m, theta, n_ell, nfold}, obj, grad, grad_z,
+                   info, value, fold_values);
+}
+
+int gps_fitc_blockloo_train_tall(gps_ctx* ctx, int objective, int nfold, int64_t nprob,
+                                 const double* X, const double* y, int64_t n, int d,
+                                 const double* Z0, int m, const double* theta0, int n_ell,
+                                 int64_t itr, double lr, double lr_z, const double* Xt,
+                                 const double* yt, int64_t nt, int flags, double* theta_out,
+                                 double* z_out, double* values, double* thetas, double* obj,
+                                 double* mu, double* var, double* sc, int* info, int* steps_done) {
+  return train_call(ctx, kFitcTallBlock,
+                    {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell, nfold}, itr, lr, lr_z,
+                    Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc, info,
+                    steps_done);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// Device helpers shared by the two batched FITC kernels, one workgroup of 256 threads per problem:
-// kernels_batch_fitc.hip (every array in LDS, n <= 128) and kernels_batch_fitc_tall.hip
-// (the n-sized arrays in a device workspace, n <= 2048).  Included once per kernel
-// file; everything sits in that file's anonymous namespace.
+// Device helpers shared by the batched FITC kernels, one workgroup of 256 threads per problem:
+// kernels_batch_fitc.hip (every array in LDS, n <= 128), kernels_batch_fitc_tall.hip
+// (the n-sized arrays in a device workspace, n <= 2048) and, through
+// batch_fitc_tall_shared.h, kernels_batch_fitc_tall_block.hip (the block-LOO objectives, DESIGN
+// §27).  Included once per kernel file; everything sits in that file's anonymous namespace.
 #pragma once
 #include "batch_driver.h"
 #include "gps_internal.h"

@@ -338,6 +338,31 @@ int64_t batch_fitc_tall_ws_doubles(int64_t n, int m);
 int batch_fitc_tall_steps(int64_t n);
 hipError_t launch_batch_fitc_tall(const BatchFitcTallParams& p, hipStream_t s);
 
+// the same batches on the block-LOO objectives GPS_BLOCK_DSS / GPS_BLOCK_KC over nfold folds
+// (kernels_batch_fitc_tall_block.hip): b.objective is the GPS_BLOCK_* code, everything
+// else in b means what it means above.  info is 0, k in 1..m (K̃mm), m + k (B) or (2 + f)·m + k
+// (the leading minor of order k of fold f's B₋f = K̃mm + Σ_{g≠f} K_gᵀΛ_g⁻¹K_g is not > 0: an
+// internal error, B₋f is K̃mm plus positive semidefinite terms).  GPS_BATCH_BLOCK_MAX_FOLDS is
+// defined below, with the full-GP block path.
+struct BatchFitcTallBlockParams {
+  BatchFitcParams b;
+  double* ws;           // [nprob][ws_stride] K, V, Ũ, F (n×(m|1) each), the nfold + 1 m×(m|1)
+                        // blocks part_f and K̃mm, then eleven n-vectors
+  int64_t ws_stride;    // >= batch_fitc_tall_block_ws_doubles(n, m, nfold)
+  int nfold;            // 2..GPS_BATCH_BLOCK_MAX_FOLDS, <= n
+  double* value;        // [nprob] BATCH_MODE_GRAD: the block objective
+  double* fold_values;  // [nprob][nfold] BATCH_MODE_GRAD: each fold's term, or NULL
+};
+size_t batch_fitc_tall_block_lds_bytes(int n, int m, int d);
+int64_t batch_fitc_tall_block_ws_doubles(int64_t n, int m, int nfold);
+// SGD steps one launch may run: batch_fitc_tall_steps' rule divided by kBatchFitcTallBlockDiv,
+// max(1, 32 / ceil(n / 128)) (32 up to n = 128, 8 at n = 500, 2 at n = 2048): a block step is about
+// two tall steps' work, and undivided the corner's longest launch measured 31 ms: a
+// function of n alone
+constexpr int kBatchFitcTallBlockDiv = 2;
+int batch_fitc_tall_block_steps(int64_t n);
+hipError_t launch_batch_fitc_tall_block(const BatchFitcTallBlockParams& p, hipStream_t s);
+
 // batches of full GPs of up to 512 rows, one workgroup per problem (kernels_batch_full_tall.hip,
 // DESIGN §24): BatchParams' model and semantics with the n×n arrays in a per-problem device
 // workspace instead of LDS and the O(n³) work on the FP64 matrix instruction, tile by tile.  Why

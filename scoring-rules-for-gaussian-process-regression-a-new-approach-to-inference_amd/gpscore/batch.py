@@ -1,6 +1,6 @@
 """Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
 (DESIGN §19, §20), and their siblings for taller problems (§22, §24; the block-LOO DSS / KC
-objectives §26).
+objectives §26 for the full GP, §27 for FITC).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
@@ -9,6 +9,8 @@ objectives §26).
                                    itr=1000, Xt=Xt, yt=yt)
     res = gpscore.train_tall(X, y, theta0, "loo_crps", lr=1.0, itr=400, Xt=Xt, yt=yt)  # n <= 512
     res = gpscore.blockloo_train_tall(X, y, theta0, "dss", nfold=4, lr=1e-3, itr=150, Xt=Xt, yt=yt)
+    res = gpscore.fitc_blockloo_train_tall(X, y, Z0, theta0, "kc", nfold=4, lr=0.1, itr=3000,
+                                           Xt=Xt, yt=yt)                                # n <= 2048
 
 The replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120, three SGD
 fits each: SD:192-231, 277-301, 372-396) and contour-plot.R's n = 20 problems are many tiny,
@@ -410,3 +412,65 @@ def fitc_train_tall(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, i
     once.  Same arguments, refusals and FitcBatchTrainResult."""
     return _fitc_train("gps_fitc_train_tall", BATCH_FITC_TALL_MAX_N, X, y, Z0, theta0, objective,
                        lr, lr_z, itr, Xt, yt, stale_noise, ctx)
+
+
+def fitc_blockloo_value_and_grad_tall(X, y, Z, theta, objective="dss", nfold=4, ctx=None):
+    """Block-LOO objective ("dss" or "kc", GP.block_loo's, over the scripts' nfold folds
+    [int(f·n/nfold), int((f+1)·n/nfold))) and its analytic gradients for B FITC GPs of 1 <= n <=
+    2048 training points at their own (θ, Z) (one gps_fitc_blockloo_grad_tall call).
+    Arguments, refusals and ``info`` as fitc_value_and_grad_tall; ``info`` (2 + f)·m + k reports an
+    internal error in fold f's factorisation.  Returns (values (B,), grads (B, 2 + n_ell), grad_Z
+    (B, m, d), fold_values (B, nfold), objectives {name: (B,)}, info (B,))."""
+    X, y = _problems(X, y, BATCH_FITC_TALL_MAX_N)
+    B, n, d = X.shape
+    Z, m = _inducing(Z, B, d)
+    th, n_ell = _thetas(theta, B, d)
+    code = _block_objective(objective)
+    nfold = _nfold(nfold, n)
+    ctx = ctx or _lib.default_context()
+    vals, fold = np.empty(B), np.empty((B, nfold))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    grad = np.empty((B, 2 + n_ell))
+    gz = np.empty((B, m, d))
+    info = np.zeros(B, np.int32)
+    ctx.call("gps_fitc_blockloo_grad_tall", code, nfold, B, ptr(X), ptr(y), n, d, ptr(Z), m,
+             ptr(th), n_ell, ptr(vals), ptr(fold), ptr(obj), ptr(grad), ptr(gz), _iptr(info))
+    return vals, grad, gz, fold, {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, info
+
+
+def fitc_blockloo_train_tall(X, y, Z0, theta0, objective="dss", nfold=4, lr=1e-3, lr_z=None,
+                             itr=3000, Xt=None, yt=None, stale_noise=False, ctx=None):
+    """fitc_train_tall on a block-LOO objective (one gps_fitc_blockloo_train_tall call): the 4-fold
+    DSS fit of "KIN40K-COMPARE-ALL-FITC-20" (K20:523-593: 3000 steps at lr = lr_z = 1e-3, the
+    defaults here) or its CRPS sibling "kc" (K20:655-726, lr = lr_z = 0.1) for B problems at once.
+    ``series["objective"]`` is the block objective before each step; everything else as
+    fitc_train_tall: arguments, refusals and FitcBatchTrainResult."""
+    X, y = _problems(X, y, BATCH_FITC_TALL_MAX_N)
+    B, n, d = X.shape
+    Z0, m = _inducing(Z0, B, d)
+    th0, n_ell = _thetas(theta0, B, d)
+    code = _block_objective(objective)
+    nfold = _nfold(nfold, n)
+    itr, lr = _steps(itr, lr)
+    lr_z = lr if lr_z is None else float(lr_z)
+    if not np.isfinite(lr_z):
+        raise ValueError(f"lr_z must be finite, got {lr_z!r}")
+    Xt, yt, nt = _tests(Xt, yt, B, d)
+    ctx = ctx or _lib.default_context()
+    nth = 2 + n_ell
+    theta, Z = np.empty((B, nth)), np.empty((B, m, d))
+    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    mu = np.empty((B, nt)) if nt else None
+    var = np.empty((B, nt)) if nt else None
+    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
+    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    ctx.call("gps_fitc_blockloo_train_tall", code, nfold, B, ptr(X), ptr(y), n, d, ptr(Z0), m,
+             ptr(th0), n_ell, itr, lr, lr_z, ptr(Xt), ptr(yt), nt,
+             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(Z), ptr(values),
+             ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
+    return FitcBatchTrainResult(
+        theta=theta, series={"objective": values, "theta": thetas},
+        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
+        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
+        info=info, steps_done=steps, Z=Z)

@@ -15,7 +15,8 @@ and 300 test points (SD:158-181) and makes three fits of each from (1, 1, 1) (SD
 "SIMPLE-FITC--comapre.py" (SF) fits the same data sets with a FITC model of m = 5 inducing inputs
 that are trained too (SF:189-237, 301-343, 420-463): run_simple_fitc, one fitc_train_batch call
 per method.  K20's own LOO-CRPS / NLML / LOO-LogS fits (n = 500, m = 20) go the same way through
-run_fitc_batch, one fitc_train_tall call per method; its DSS and KC fits stay with run.  KF's
+run_fitc_batch, one fitc_train_tall call per method; its block-LOO DSS and KC fits through
+run_fitc_blockloo_batch, one fitc_blockloo_train_tall call per method.  KF's
 LOO-CRPS / NLML / LOO-LogS fits (full GP, n = 500) have a batch route as well: run_full_batch, one
 train_tall call per method for all replicates; its block-LOO DSS fit goes through
 run_full_blockloo_batch, one blockloo_train_tall call for all replicates, and only its ES fit
@@ -35,8 +36,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
-from .batch import (BLOCK_BATCH_OBJS, blockloo_train_tall, fitc_train_batch, fitc_train_tall,
-                    train_batch, train_tall)
+from .batch import (BLOCK_BATCH_OBJS, blockloo_train_tall, fitc_blockloo_train_tall,
+                    fitc_train_batch, fitc_train_tall, train_batch, train_tall)
 from .gp import GP
 
 SHEETS = ("trainx", "trainy", "testx", "testy")
@@ -481,4 +482,68 @@ def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, re
                                       f"{int(res.steps_done[q])} steps")
         out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
         out[name]["theta"] = res.theta.copy()
+    return out
+
+
+def run_fitc_blockloo_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=None, reseed=True,
+                            stale_noise=True, ctx=None, nfold=4):
+    """run_fitc_batch for K20's block-LOO fits → {method: {metric: array(TT), "Z": array(TT, m, d),
+    "theta": array(TT, 2 + n_ell), "failed": array(TT, bool)}}: every method's TT FITC fits on the
+    nfold-fold block-LOO DSS or KC objective (n = 500, m inducing inputs trained too), the test
+    predictive and the score bundle are ONE fitc_blockloo_train_tall call, one workgroup per
+    replicate.  ``methods`` defaults to the dss and kc entries of K20_METHODS
+    (K20:523-593, K20:655-726: 3000 steps each); a method whose objective is pointwise raises
+    ValueError (use run_fitc_batch), one whose objective is es raises too (use run(kind="fitc")).
+    Data replicates and starting points are drawn in run's order — replicate-major, then method,
+    initial_theta first and Z0 second, U(0,1) or N(0,1) by the method's z_init — so with the same
+    ``seed``, ``reseed=True`` and the same method subset run(kind="fitc", methods=subset) and this
+    fit the same problems.  ``itr`` overrides the methods' step counts; stale_noise as run_method.
+    A kc replicate whose factorisation fails gets zero metrics as in run_method (K20:784-790); a
+    dss replicate that fails raises NotPositiveDefinite."""
+    if methods is None:
+        methods = {k: K20_METHODS[k] for k in ("dss", "kc")}
+    for name, meth in methods.items():
+        if meth.objective not in BLOCK_BATCH_OBJS:
+            route = "run(kind=\"fitc\")" if meth.objective == "es" else "run_fitc_batch"
+            raise ValueError(f"run_fitc_blockloo_batch: method {name!r} has objective "
+                             f"{meth.objective!r}, not one of {BLOCK_BATCH_OBJS}; use {route} for it")
+    if int(TT) != TT or TT < 1:
+        raise ValueError(f"TT must be a positive integer, got {TT!r}")
+    if int(m) != m or m < 1:
+        raise ValueError(f"m must be a positive integer, got {m!r}")
+    TT, m = int(TT), int(m)
+    rng = np.random.default_rng(seed)
+    rs = None if reseed else random.Random()
+    n_pool = sheets["trainx"].shape[0]
+    data, th0, Z0 = [], {name: [] for name in methods}, {name: [] for name in methods}
+    for j in range(TT):
+        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
+        data.append(dd)
+        d = dd["train_x"].shape[1]
+        for name, meth in methods.items():
+            k, ell, noise = initial_theta(meth, d, rng)
+            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
+            Z0[name].append(rng.random((m, d)) if meth.z_init == "rand"
+                            else rng.standard_normal((m, d)))
+    X = np.stack([dd["train_x"] for dd in data])
+    y = np.stack([dd["train_y"] for dd in data])
+    Xt = np.stack([dd["test_x"] for dd in data])
+    yt = np.stack([dd["test_y"] for dd in data])
+    out = {}
+    for name, meth in methods.items():
+        res = fitc_blockloo_train_tall(X, y, np.stack(Z0[name]), np.stack(th0[name]),
+                                       meth.objective, nfold=nfold, lr=meth.lr, lr_z=meth.lr_z,
+                                       itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
+                                       stale_noise=stale_noise, ctx=ctx)
+        failed = np.asarray(res.info) != 0
+        if failed.any() and meth.objective != "kc":
+            q = int(np.flatnonzero(failed)[0])
+            raise NotPositiveDefinite(int(res.info[q]), f"run_fitc_blockloo_batch: method {name!r}, "
+                                      f"replicate {q}: info = {int(res.info[q])} (k: the leading "
+                                      f"minor of order k of K(Z,Z) + 1e-3 I, m + k: of B, (2 + f) m "
+                                      f"+ k: of fold f's B) after {int(res.steps_done[q])} steps")
+        out[name] = {k: np.where(failed, 0.0, res.scores["test_" + k]) for k in METRICS}
+        out[name]["Z"] = res.Z.copy()
+        out[name]["theta"] = res.theta.copy()
+        out[name]["failed"] = failed
     return out
