@@ -149,6 +149,20 @@ enum {
                              and for the r pre-pass behind Lb's L11 block at ≤ 4096 tiles;
                              0: the row norms after the factorisation.  Same tiles, same values
                              bitwise. */
+  GPS_OPT_DAG_TILES_FULL = 28, /* largest block (in 128-tiles, 2..64; default 40) the persistent
+                             factorisation takes in the full GP's fit; 0: GPS_OPT_DAG_TILES.
+                             Every other factorisation (FITC m×m, gps_potrf_diag, the block-LOO
+                             folds) keeps GPS_OPT_DAG_TILES. */
+  GPS_OPT_DAG_KBATCH = 29,  /* persistent factorisation: B | g << 4 [| 256] — the UPD / UPDX terms
+                             of one tile run as single products over up to B adjacent K tiles (B
+                             in 2..8), the last g (0..3) terms of every tile staying single
+                             tasks; with 256 only in blocks of more than GPS_OPT_DAG_TILES tiles
+                             (those GPS_OPT_DAG_TILES_FULL admits: smaller blocks are bound by
+                             their leaf chain and gain nothing).  B = 0 or 1: every term a task
+                             of its own, the queue of before.  Default 8 | 256.  Same algorithm,
+                             other summation order within a batch; for a given value the bits do
+                             not depend on the queue order, the workgroup count or the load
+                             group. */
 };
 int gps_ctx_set_option(gps_ctx* ctx, int key, int value);
 
@@ -173,6 +187,11 @@ int gps_ctx_stats(gps_ctx* ctx, int64_t* out, int cap);
  * bits rejected — kernels_potrf.hip).  Returns the queue length (writes at most cap words);
  * needs no device. */
 int gps_dag_task_list(int T, int flags, uint32_t* out, int cap);
+/* The same with K batches (GPS_OPT_DAG_KBATCH): kb in 1..8 terms per UPD / UPDX task, the last
+ * kg in 0..3 terms of every tile single.  i, j, k take 6 bits each; the batch length − 1 sits in
+ * bits 14-15 (low two) and 22 (high), k (UPD) resp. j (UPDX) naming the batch's first term.
+ * kb = 1 gives gps_dag_task_list's words exactly. */
+int gps_dag_task_list_ex(int T, int flags, int kb, int kg, uint32_t* out, int cap);
 
 /* Diagnostics: ONE internal FP64 GEMM launch (csrc/kernels_gemm.hip's launch_gemm, through the
  * same gemm() every production caller uses, on the context's main stream with that stream's

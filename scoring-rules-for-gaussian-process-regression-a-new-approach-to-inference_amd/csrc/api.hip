@@ -289,11 +289,23 @@ int fitc_rowsq_dep(gps_ctx* ctx, const double* L, int* sig, int64_t ncols, int m
 
 // the task list of an nb-tile persistent block under the context's options
 int dag_list_key(const gps_ctx* ctx, int64_t nb) {
-  return (int)(3 * nb + ctx->dag_order);
+  return (int)(3 * nb + ctx->dag_order) << 8 | dag_kg(ctx, nb) << 4 | dag_kb(ctx, nb);
 }
+// the K batches of an nb-tile block's task list (GPS_OPT_DAG_KBATCH): at most B terms, the last g
+// single; with bit 8 set only in blocks above GPS_OPT_DAG_TILES — smaller ones are bound by
+// their leaf chain, which batches of 8 only delay (2560 columns: 1.05 -> 1.15 ms)
+int dag_kb(const gps_ctx* ctx, int64_t nb) {
+  if ((ctx->dag_kbatch & 256) && nb <= ctx->dag_tiles) return 1;
+  return std::max(1, ctx->dag_kbatch & 15);
+}
+int dag_kg(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->dag_kbatch >> 4 & 3 : 0; }
 
-// a block of nb 128-tiles goes to the persistent factorisation (GPS_OPT_DAG)
-bool dag_block(const gps_ctx* ctx, int64_t nb) { return ctx->dag && nb >= 2 && nb <= ctx->dag_tiles; }
+// a block of nb 128-tiles goes to the persistent factorisation (GPS_OPT_DAG); the full GP's
+// factorisation has a cap of its own (GPS_OPT_DAG_TILES_FULL)
+bool dag_block(const gps_ctx* ctx, int64_t nb) {
+  const int cap = ctx->dag_full && ctx->dag_tiles_full ? ctx->dag_tiles_full : ctx->dag_tiles;
+  return ctx->dag && nb >= 2 && nb <= cap;
+}
 
 // the block sizes the recursion of an nb-tile factorisation hands to the persistent kernel, and
 // how many counter ints all of them need together
@@ -351,6 +363,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     d.cnt = static_cast<int*>(ctx->dag_cnt.p) + ctx->dag_cnt_used;
     d.spin_ticks = 200000000ull;  // 2 s at the 100 MHz real-time clock
     d.group = ctx->dag_group;
+    d.kbatch = dag_kb(ctx, nb);
     d.sig = ctx->dag_sig;  // (a dependent row-norm launch reads its rows: the first block only)
     ctx->dag_sig = nullptr;
     ctx->dag_cnt_used += need;
@@ -527,7 +540,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
   for (int T : dsizes) {
     const int lk = dag_list_key(ctx, T);
     if (ctx->dag_lists.count(lk)) continue;
-    const std::vector<uint32_t> tl = dag_task_list(T, ctx->dag_order, true);
+    const std::vector<uint32_t> tl = dag_task_list(T, ctx->dag_order, true, dag_kb(ctx, T), dag_kg(ctx, T));
     auto& e = ctx->dag_lists[lk];
     HIPCHK(ensure(ctx, e.first, tl.size() * 4));
     // (stream-ordered, never the legacy stream: another context of this process may be
@@ -566,7 +579,8 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
       pre ? (uintptr_t)ctx->pre.n1 : 0, pre ? (uintptr_t)ctx->aux[0] : 0,
       pre ? (uintptr_t)ctx->Knm.p : 0, pre ? (uintptr_t)ctx->fslab.p : 0,
       pre ? (uintptr_t)ctx->fn_pad : 0, pre ? (uintptr_t)ctx->m_pad : 0, pre ? (uintptr_t)ctx->pre.sig : 0,
-      (uintptr_t)ctx->dag, (uintptr_t)ctx->dag_tiles, (uintptr_t)ctx->dag_group, (uintptr_t)ctx->dag_wgs, (uintptr_t)ctx->dag_half,
+      (uintptr_t)ctx->dag, (uintptr_t)ctx->dag_tiles,
+      (uintptr_t)(ctx->dag_full ? ctx->dag_tiles_full : 0), (uintptr_t)ctx->dag_kbatch, (uintptr_t)ctx->dag_group, (uintptr_t)ctx->dag_wgs, (uintptr_t)ctx->dag_half,
       (uintptr_t)ctx->dag_cnt.p, (uintptr_t)ctx->sk_cnt.p, (uintptr_t)ctx->dag_sig};
   for (int T : dsizes) key.push_back((uintptr_t)ctx->dag_lists[dag_list_key(ctx, T)].first.p);  // the task lists
   for (auto& g : ctx->pgraphs)
@@ -832,6 +846,15 @@ int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
       ARGCHK(value >= 2 && value <= 64, "GPS_OPT_DAG_TILES must be in 2..64");
       ctx->dag_tiles = value;
       return 0;
+    case GPS_OPT_DAG_TILES_FULL:
+      ARGCHK(value == 0 || (value >= 2 && value <= 64), "GPS_OPT_DAG_TILES_FULL must be 0 or in 2..64");
+      ctx->dag_tiles_full = value;
+      return 0;
+    case GPS_OPT_DAG_KBATCH:
+      ARGCHK(value >= 0 && (value & 15) <= 8 && (value >> 4 & 15) <= 3 && (value >> 9) == 0,
+             "GPS_OPT_DAG_KBATCH must be B | g << 4 [| 256] with B in 0..8 and g in 0..3");
+      ctx->dag_kbatch = (value & 15) < 2 ? 0 : value;
+      return 0;
     default: return fail(ctx, -1, "unknown option");
   }
 }
@@ -861,10 +884,14 @@ int gps_ctx_stats(gps_ctx* ctx, int64_t* out, int cap) {
 }
 
 int gps_dag_task_list(int T, int flags, uint32_t* out, int cap) {
-  if (T < 2 || T > 64 || cap < 0 || (cap > 0 && !out) || (flags & ~13))
+  return gps_dag_task_list_ex(T, flags, 1, 0, out, cap);
+}
+
+int gps_dag_task_list_ex(int T, int flags, int kb, int kg, uint32_t* out, int cap) {
+  if (T < 2 || T > 64 || cap < 0 || (cap > 0 && !out) || (flags & ~13) || kb < 1 || kb > 8 || kg < 0 || kg > 3)
     return fail(nullptr, -1, "bad arguments");
   const std::vector<uint32_t> tl = dag_task_list(T, (flags >> 2 & 3) == 0 ? 1 : (flags >> 2 & 3) == 3 ? 0 : flags >> 2 & 3,
-                                                 (flags & 1) != 0);
+                                                 (flags & 1) != 0, kb, kg);
   for (int i = 0; i < cap && i < (int)tl.size(); ++i) out[i] = tl[i];
   return (int)tl.size();
 }

@@ -450,9 +450,13 @@ struct DagParams {
   int* sig = nullptr;              // row-ready signals for a dependent row-norm launch (kSig*):
                                    // +1 per started workgroup, row tile i flagged once L⁻¹'s row
                                    // tile i is final (LEAF(0); the last FIN(i, ·) strip)
+  int kbatch = 1;                  // the longest K batch in the task list (1..8; host-side bound
+                                   // check of the batched strips' buffer descriptors only)
 };
 hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s);
-std::vector<uint32_t> dag_task_list(int T, int order = 1, bool fine = true);
+// kb: UPD / UPDX terms of one tile in batches of at most kb (1: every term its own task, the
+// list of before); kg: the last kg terms of every tile stay single tasks
+std::vector<uint32_t> dag_task_list(int T, int order = 1, bool fine = true, int kb = 1, int kg = 0);
 inline int64_t dag_cnt_ints(int T) { return (16 + 2 * (int64_t)T * T + 63) / 64 * 64; }
 
 // y[i] = sum_k L[i][k] x[k] over the tile-lower part (rows < n_pad)

@@ -472,7 +472,11 @@ __global__ __launch_bounds__(256) void potrf_leaf_v4_kernel(
 //   UPDX(i,k,j)    S_ik (+)= L_ij · X_jk  (first term: =)      i > j ≥ k      (4 row strips)
 //   FIN(i,k)       X_ik  = −X_ii · S_ik   (in place)           i > k          (4 column strips)
 // (right-looking Cholesky; the inverse right-looking too: X_ik = −X_ii Σ_{j=k}^{i−1} L_ij X_jk,
-// S_ik accumulated in X's own tile).  Each strip task runs on 4 waves, each a 32×32 block of
+// S_ik accumulated in X's own tile).  K batches: the UPD terms k0 ≤ k < k1 of a
+// tile read adjacent column ranges of the same two row blocks of A, and the UPDX terms
+// j0 ≤ j < j1 adjacent columns of L's row block and adjacent rows of X's column, so one task runs
+// them as ONE product with K = 128·(k1 − k0): one fetch, one wait, one C round trip and one
+// hand-off for up to 8 terms (+U per term, as before).  Each strip task runs on 4 waves, each a 32×32 block of
 // v_mfma_f64_16x16x4 with its operands streamed from L2 (no LDS), the K range clipped to the
 // triangular operand's nonzeros.  Arrival counters per tile: A-side acnt[i][j] (+4 per UPD, +4
 // per TRSM, +1 per LEAF) and X-side xcnt[i][k] (+4 per UPDX / FIN, +1 per LEAF); a task polls
@@ -521,7 +525,8 @@ __device__ __forceinline__ void wave_gemm32(const double* Ap, int64_t lda, const
                                             int64_t ldb, int kb, int ke, d4 (&acc)[2][2]) {
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   const __amdgpu_buffer_rsrc_t ra = rsrc(Ap, (uint32_t)(32 * lda * 8));
-  const __amdgpu_buffer_rsrc_t rb = rsrc(Bp, (uint32_t)((BT ? 32 : 128) * ldb * 8));
+  // (B stored [k][j]: the k rows the product reads — 128, or a K batch's 128·len)
+  const __amdgpu_buffer_rsrc_t rb = rsrc(Bp, (uint32_t)((BT ? 32 : ke > 128 ? ke : 128) * ldb * 8));
   typedef double Frag[G][2][4];  // [chunk in group][16-block][k step]
   const int nc = (ke - kb) / 16;
   auto load_group = [&](int c, Frag& a, Frag& b) {
@@ -782,8 +787,10 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
         trow[3] = (unsigned long long)blockIdx.x << 8 | (xcc & 15);
       }
     }
-    const int type = w & 7, part = (w >> 3) & 15, fine = (w >> 7) & 1, ti = (w >> 8) & 255,
-              tj = (w >> 16) & 255, tk = (w >> 24) & 255;
+    const int type = w & 7, part = (w >> 3) & 15, fine = (w >> 7) & 1, ti = (w >> 8) & 63,
+              tj = (w >> 16) & 63, tk = (w >> 24) & 63;
+    // K batch of an UPD / UPDX strip (dag_task_list): terms tk .. tk + len − 1, resp. tj ..
+    const int len = 1 + (int)((w >> 14) & 3) + 4 * (int)((w >> 22) & 1);
     // ---- the counts this task needs (see the header); up to three, polled by wave 0 (every
     //      lane loads the same word; the exit test is taken on lane 0's view)
     if (wave == 0) {
@@ -797,16 +804,23 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
           c0 = acnt + ti * T + tk; v0 = U * tk;
           c1 = xcnt + tk * T + tk; v1 = 1;
           break;
-        case 2:  // UPD(i, j, k)
-          c0 = acnt + ti * T + tk; v0 = U * (tk + 1);
-          c1 = acnt + tj * T + tk; v1 = U * (tk + 1);
+        // (a K batch polls its LAST term's operands: L_ik final means TRSM(i, k) ran, which waited
+        //  for every UPD(i, k, k') — each of which had polled L_ik' final; X_jk likewise through
+        //  FIN(j, k) and the UPDX(j, k, j') — so the last counts imply the others)
+        case 2: {  // UPD(i, j, k .. kl)
+          const int kl = tk + len - 1;
+          c0 = acnt + ti * T + kl; v0 = U * (kl + 1);
+          c1 = acnt + tj * T + kl; v1 = U * (kl + 1);
           c2 = acnt + ti * T + tj; v2 = U * tk;
           break;
-        case 3:  // UPDX(i, k, j): L_ij final, X_jk final, S_ik's earlier terms
-          c0 = acnt + ti * T + tj; v0 = U * (tj + 1);
-          c1 = xcnt + tj * T + tk; v1 = tj == tk ? 1 : U * (tj - tk + 1);
+        }
+        case 3: {  // UPDX(i, k, j .. jl): L_ij final, X_jk final, S_ik's earlier terms
+          const int jl = tj + len - 1;
+          c0 = acnt + ti * T + jl; v0 = U * (jl + 1);
+          c1 = xcnt + jl * T + tk; v1 = jl == tk ? 1 : U * (jl - tk + 1);
           c2 = xcnt + ti * T + tk; v2 = U * (tj - tk);
           break;
+        }
         case 4:  // FIN(i, k)
           c0 = xcnt + ti * T + tk; v0 = U * (ti - tk);
           c1 = xcnt + ti * T + ti; v1 = 1;
@@ -911,9 +925,10 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
           st.A = p.A + (R + q) * lda + K; st.lda = lda;
           st.B = p.A + (J + wv) * lda + K; st.ldb = lda; st.bt = 1;
           st.C = p.A + (R + q) * lda + J + wv; st.ldc = lda;
-          st.alpha = -1.0; st.beta = 1.0; st.kb = 0; st.ke = 128;
+          st.alpha = -1.0; st.beta = 1.0; st.kb = 0; st.ke = 128 * len;  // (the batch: one product)
           st.active = !(ti == tj && wave > part);
           out = acnt + ti * T + tj;
+          inc = len * (U / NP);  // the counters keep meaning "U per applied term"
           break;
         }
         case 3: {  // UPDX(i, k, j): row strip q of S_ik (+)= L_ij X_jk (X_kk lower: k' >= col)
@@ -922,8 +937,9 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
           st.B = p.Linv + J * ldl + K + wv; st.ldb = ldl; st.bt = 0;
           st.C = p.Linv + (R + q) * ldl + K + wv; st.ldc = ldl;
           st.alpha = 1.0; st.beta = tj == tk ? 0.0 : 1.0;
-          st.kb = tj == tk ? (int)wv : 0; st.ke = 128;
+          st.kb = tj == tk ? (int)wv : 0; st.ke = 128 * len;  // (rows J .. J + 128·len of X's column)
           out = xcnt + ti * T + tk;
+          inc = len * (U / NP);
           break;
         }
         default: {  // FIN(i, k): column strip q of X_ik = −X_ii S_ik, rows wv.. (X_ii lower)
@@ -979,10 +995,11 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
 
 hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s) {
   if ((p.lda & 1) || (p.ldl & 1) || (p.Lout && (p.ldlo & 1)) || p.T < 1 || p.T > 64 || nwg < 1 ||
-      !p.tasks || !p.cnt || p.ntasks < 1)
+      !p.tasks || !p.cnt || p.ntasks < 1 || p.kbatch < 1 || p.kbatch > 8)
     return hipErrorInvalidValue;
-  // every strip's buffer descriptor spans at most 128 rows of its matrix (32-bit offsets)
-  if ((int64_t)128 * std::max(p.lda, p.ldl) * 8 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  // every strip's buffer descriptor spans at most 128 rows of its matrix, 128·kbatch for a
+  // batched UPDX's B operand (32-bit offsets)
+  if ((int64_t)128 * p.kbatch * std::max(p.lda, p.ldl) * 8 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
   auto k = p.trace ? (p.group == 2 ? dag::potrf_dag_kernel<true, 2>
                                     : p.group == 3 ? dag::potrf_dag_kernel<true, 3> : dag::potrf_dag_kernel<true, 4>)
                    : (p.group == 2 ? dag::potrf_dag_kernel<false, 2>
@@ -1006,22 +1023,35 @@ hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s) {
 // (Round 4's split chain — the leaf without its inverse, TRSM(k+1,k) by substitution, an INV task
 // off the chain — measured slower and was removed: profiles/r4_dag_split_ab.txt,
 // profiles/r5_prune_split_chain.diff.)
-// Word: type | part << 3 | fine << 7 | i << 8 | j << 16 | k << 24.
+// Word: type | part << 3 | fine << 7 | i << 8 | j << 16 | k << 24, i, j, k in 6 bits each; the K
+// batch length − 1 of an UPD / UPDX task (0..7) in bits 14-15 (low) and 22 (high),
+// k resp. j its first term — length field 0 is the single-term task of before.
 // order 1's weights, µs: LEAF, fine part, TRSM, UPD, UPDX, FIN strips, hand-off (tools/dag_bench
 // overrides them for sweeps; the library never writes them)
 double g_dag_weights[7] = {35.0, 6.0, 9.7, 11.7, 11.2, 9.3, 2.5};
 
-std::vector<uint32_t> dag_task_list(int T, int order, bool fine) {
-  struct Task { int type, i, j, k; std::vector<int> deps; double est = 0.0, rank = 0.0; };
+std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg) {
+  // len: the K batch of an UPD / UPDX task (terms k .. k + len − 1, resp. j .. j + len − 1)
+  struct Task { int type, i, j, k, len; std::vector<int> deps; double est = 0.0, rank = 0.0; };
   auto is_fine = [&](const Task& t) {
     return fine && ((t.type == 1 && t.i == t.k + 1) || (t.type == 2 && t.i == t.k + 1 && t.j == t.i));
+  };
+  // K batches: of the nt terms of a tile, numbered in the order they are applied,
+  // the first nt − keep go in runs of kb from term 0 (the last run shortened) and the last keep
+  // stay single — a function of (kb, kg, the tile) alone, never of the order or the width.
+  // [b0, b1): the run of term t.
+  auto batch_of = [&](int t, int nt, int keep, int& b0, int& b1) {
+    const int nbat = kb > 1 ? std::max(0, nt - keep) : 0;
+    if (t >= nbat) { b0 = t; b1 = t + 1; return; }
+    b0 = t / kb * kb;
+    b1 = std::min(b0 + kb, nbat);
   };
   std::vector<Task> tk;
   std::vector<int> leaf(T), xkk(T), trsm(T * T, -1), fin(T * T, -1);
   std::vector<int> upd_last(T * T, -1), updx_last(T * T, -1);
-  auto add = [&](int type, int i, int j, int k, std::vector<int> deps) {
+  auto add = [&](int type, int i, int j, int k, int len, std::vector<int> deps) {
     Task t;
-    t.type = type; t.i = i; t.j = j; t.k = k;
+    t.type = type; t.i = i; t.j = j; t.k = k; t.len = len;
     for (int d : deps)
       if (d >= 0) t.deps.push_back(d);
     tk.push_back(t);
@@ -1029,21 +1059,38 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine) {
   };
   // factorisation, right-looking (generation order is topological)
   for (int k = 0; k < T; ++k) {
-    leaf[k] = add(0, k, k, k, {upd_last[k * T + k]});
+    leaf[k] = add(0, k, k, k, 1, {upd_last[k * T + k]});
     xkk[k] = leaf[k];  // the task X_kk comes from
-    for (int i = k + 1; i < T; ++i) trsm[i * T + k] = add(1, i, k, k, {upd_last[i * T + k], xkk[k]});
+    for (int i = k + 1; i < T; ++i) trsm[i * T + k] = add(1, i, k, k, 1, {upd_last[i * T + k], xkk[k]});
     for (int j = k + 1; j < T; ++j)
-      for (int i = j; i < T; ++i)
-        upd_last[i * T + j] = add(2, i, j, k, {trsm[i * T + k], trsm[j * T + k], upd_last[i * T + j]});
+      for (int i = j; i < T; ++i) {
+        // tile (i, j)'s terms k' < j; the chain's UPD(k+1,k+1,k) is a tile's last term and stays
+        // a fine task of its own.  A batch is generated with its last term, when every L it reads
+        // exists.
+        int b0, b1;
+        batch_of(k, j, std::max(kg, fine && i == j ? 1 : 0), b0, b1);
+        if (k != b1 - 1) continue;
+        std::vector<int> deps = {upd_last[i * T + j]};
+        for (int q = b0; q < b1; ++q) { deps.push_back(trsm[i * T + q]); deps.push_back(trsm[j * T + q]); }
+        if (b1 - b0 == 1) deps = {trsm[i * T + k], trsm[j * T + k], upd_last[i * T + j]};
+        upd_last[i * T + j] = add(2, i, j, b0, b1 - b0, deps);
+      }
   }
   // inverse: X row j final → its terms pushed into every row i > j
   auto xfinal = [&](int j, int k) { return j == k ? xkk[k] : fin[j * T + k]; };
   for (int j = 0; j < T; ++j) {
     for (int k = 0; k < j; ++k)  // X_jk = −X_jj S_jk once every term j' < j is in
-      fin[j * T + k] = add(4, j, k, k, {updx_last[j * T + k], xkk[j]});
+      fin[j * T + k] = add(4, j, k, k, 1, {updx_last[j * T + k], xkk[j]});
     for (int i = j + 1; i < T; ++i)
-      for (int k = 0; k <= j; ++k)
-        updx_last[i * T + k] = add(3, i, j, k, {trsm[i * T + j], xfinal(j, k), updx_last[i * T + k]});
+      for (int k = 0; k <= j; ++k) {
+        int b0, b1;  // tile (i, k)'s terms j' in [k, i), numbered from k
+        batch_of(j - k, i - k, kg, b0, b1);
+        if (j - k != b1 - 1) continue;
+        std::vector<int> deps = {updx_last[i * T + k]};
+        for (int q = b0 + k; q < b1 + k; ++q) { deps.push_back(trsm[i * T + q]); deps.push_back(xfinal(q, k)); }
+        if (b1 - b0 == 1) deps = {trsm[i * T + j], xfinal(j, k), updx_last[i * T + k]};
+        updx_last[i * T + k] = add(3, i, b0 + k, k, b1 - b0, deps);
+      }
   }
   const int n = (int)tk.size();
   std::vector<std::vector<int>> succ(n);
@@ -1051,12 +1098,12 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine) {
   for (int t = 0; t < n; ++t)
     for (int d : tk[t].deps) { succ[d].push_back(t); ++indeg[t]; }
   if (order == 0) {
-    auto dur = [&](const Task& t) { return t.type == 0 ? 36.0 : 4.0; };
+    auto dur = [&](const Task& t) { return t.type == 0 ? 36.0 : 4.0 * t.len; };
     for (int t = 0; t < n; ++t)  // generation order is topological
       for (int d : tk[t].deps) tk[t].est = std::max(tk[t].est, tk[d].est + dur(tk[d]) + 3.0);
   } else if (order == 2) {  // round 3's weights
     auto dur = [&](const Task& t) {
-      return t.type == 0 ? 38.0 : is_fine(t) ? 4.0 : 9.0;
+      return t.type == 0 ? 38.0 : is_fine(t) ? 4.0 : 9.0 * t.len;
     };
     for (int t = n - 1; t >= 0; --t) {
       double m = 0.0;
@@ -1074,8 +1121,8 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine) {
       switch (t.type) {
         case 0: return w[0];
         case 1: return w[2];
-        case 2: return w[3];
-        case 3: return w[4];
+        case 2: return w[3] * t.len;  // (a K batch weighs as its K)
+        case 3: return w[4] * t.len;
         default: return w[5];
       }
     };
@@ -1099,7 +1146,8 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine) {
     const int parts = x.type == 0 ? 1 : !f ? dag::NP : x.type == 1 ? dag::NPF_TRSM : dag::NPF_UPD;
     for (int q = 0; q < parts; ++q)
       out.push_back((uint32_t)x.type | (uint32_t)q << 3 | (uint32_t)f << 7 | (uint32_t)x.i << 8 |
-                    (uint32_t)x.j << 16 | (uint32_t)x.k << 24);
+                    (uint32_t)((x.len - 1) & 3) << 14 | (uint32_t)x.j << 16 |
+                    (uint32_t)((x.len - 1) >> 2) << 22 | (uint32_t)x.k << 24);
     for (int s2 : succ[t])
       if (!--indeg[s2]) ready.push({tk[s2].est, s2});
   }

@@ -2,7 +2,12 @@
 // of T 128-tiles, standalone: timing over repeated launches, a sampled correctness check
 // (L·Lᵀ = A and L⁻¹·L = I on random entries), and one traced launch whose per-slot timestamps
 // go to a CSV for tools/dag_trace.py (critical path, hand-off latencies, per-type durations).
-//   dag_bench [T=20] [nwg=256] [trace.csv|-] [reps=20] [group=3] [order=1] [fine=1]
+//   dag_bench [T=20] [nwg=256] [trace.csv|-] [reps=20] [group=3] [order=1] [fine=1] [weights|-]
+//             [B=1] [g=0]
+// B, g: the K batches of the UPD / UPDX tasks (GPS_OPT_DAG_KBATCH).  A traced launch always runs:
+// the bulk strip-task rate printed beside the block time is the flops of the UPD / UPDX strip
+// tasks over their fetch-to-done time, summed over the workgroups (what the off-chain tasks
+// sustain, waits included), with the mean fetch-to-done and ready-to-done time per strip task.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -25,7 +30,10 @@ int main(int argc, char** argv) {
   const int group = argc > 5 ? atoi(argv[5]) : 3;
   const int order = argc > 6 ? atoi(argv[6]) : 1;
   const int fine = argc > 7 ? atoi(argv[7]) : 1;
-  if (argc > 8) {  // order 1's weights: LEAF,fine,TRSM,UPD,UPDX,FIN,hand-off
+  const int kb = argc > 9 ? atoi(argv[9]) : 1;
+  const int kg = argc > 10 ? atoi(argv[10]) : 0;
+  if (kb < 1 || kb > 8 || kg < 0 || kg > 3) { fprintf(stderr, "B in 1..8, g in 0..3\n"); return 2; }
+  if (argc > 8 && argv[8][0] != '-') {  // order 1's weights: LEAF,fine,TRSM,UPD,UPDX,FIN,hand-off
     double* w = gps::g_dag_weights;
     if (sscanf(argv[8], "%lf,%lf,%lf,%lf,%lf,%lf,%lf", w, w + 1, w + 2, w + 3, w + 4, w + 5, w + 6) != 7) {
       fprintf(stderr, "weights: 7 comma-separated numbers\n");
@@ -44,7 +52,7 @@ int main(int argc, char** argv) {
       for (int k = 0; k < d; ++k) { const double t = X[i * d + k] - X[j * d + k]; s += t * t; }
       h[(size_t)i * n + j] = exp(-0.25 * s) + (i == j ? 0.05 : 0.0);
     }
-  const std::vector<uint32_t> tl = dag_task_list(T, order, fine != 0);
+  const std::vector<uint32_t> tl = dag_task_list(T, order, fine != 0, kb, kg);
   const int nt = (int)tl.size();
   double *A0, *A, *Li, *ld;
   int *info, *cnt;
@@ -63,7 +71,7 @@ int main(int argc, char** argv) {
   DagParams p;
   p.A = A; p.lda = n; p.Linv = Li; p.ldl = n; p.Lout = nullptr; p.ldlo = 0;
   p.logdiag = ld; p.info = info; p.base = 0; p.nreal = n; p.T = T;
-  p.tasks = tasks; p.ntasks = nt; p.cnt = cnt; p.spin_ticks = 200000000ull; p.group = group;
+  p.tasks = tasks; p.ntasks = nt; p.cnt = cnt; p.spin_ticks = 200000000ull; p.group = group; p.kbatch = kb;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   auto launch = [&](bool tr, float* ms) {
@@ -115,16 +123,40 @@ int main(int argc, char** argv) {
   double lsum = 0;
   for (double x : gld) lsum += x;
   const double fl = 2.0 * n * (double)n * n / 3.0;
-  printf("group=%d order=%d fine=%d w=%s ", group, order, fine, argc > 8 ? argv[8] : "-");
+  printf("group=%d order=%d fine=%d w=%s B=%d g=%d ", group, order, fine, argc > 8 ? argv[8] : "-", kb, kg);
   printf("T=%d n=%d nwg=%d tasks=%d: median %.3f ms (min %.3f, max %.3f) = %.1f us/tile, %.2f TF/s; "
          "max|XAX^T - I| %.2e over 24 samples, sum log L_ii %.6f\n",
          T, n, nwg, nt, ts[ts.size() / 2], ts[0], ts.back(), 1e3 * ts[ts.size() / 2] / T,
          fl / (ts[ts.size() / 2] * 1e-3) / 1e12, err, lsum);
-  if (tpath) {
+  {
     float ms;
     launch(true, &ms);
     std::vector<unsigned long long> tr((size_t)nt * 4);
     CK(hipMemcpy(tr.data(), trace, (size_t)nt * 32, hipMemcpyDeviceToHost));
+    double bflop = 0.0, bticks = 0.0, rticks = 0.0;
+    long nb = 0;
+    for (int t = 0; t < nt; ++t) {
+      const uint32_t w = tl[t];
+      const int type = w & 7, part = (w >> 3) & 15, fn = (w >> 7) & 1, i = (w >> 8) & 63, j = (w >> 16) & 63,
+                k = (w >> 24) & 63, len = 1 + ((w >> 14) & 3) + 4 * ((w >> 22) & 1);
+      if (fn || (type != 2 && type != 3)) continue;
+      // 32×32 blocks the strip's four waves run: UPD on a diagonal tile the lower ones only; the
+      // first UPDX term starts at the wave's own column (X_kk lower)
+      double f = 0.0;
+      for (int wv = 0; wv < 4; ++wv) {
+        if (type == 2 && i == j && wv > part) continue;
+        f += 2.0 * 32 * 32 * (128.0 * len - (type == 3 && j == k ? 32.0 * wv : 0.0));
+      }
+      bflop += f;
+      bticks += (double)(tr[4 * t + 2] - tr[4 * t]);
+      rticks += (double)(tr[4 * t + 2] - tr[4 * t + 1]);
+      ++nb;
+    }
+    // ticks are 10 ns; the tasks of one workgroup run one after another, nwg of them side by side
+    printf("bulk strip tasks (traced launch %.3f ms): %ld UPD/UPDX strips, %.2f us fetch-to-done, %.2f us "
+           "ready-to-done, %.1f TF/s over %d workgroups\n", ms, nb, bticks / nb * 1e-2, rticks / nb * 1e-2,
+           bflop / (bticks * 1e-8) * nwg / 1e12, nwg);
+    if (!tpath) return err < 1e-8 ? 0 : 3;
     FILE* f = fopen(tpath, "w");
     fprintf(f, "slot,word,fetch,ready,done,wg,xcc\n");
     for (int t = 0; t < nt; ++t)

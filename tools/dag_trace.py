@@ -15,8 +15,9 @@ def load(path):
     rows = []
     for r in csv.DictReader(open(path)):
         w = int(r["word"])
-        rows.append(dict(slot=int(r["slot"]), type=w & 7, part=(w >> 3) & 15, fine=(w >> 7) & 1, i=(w >> 8) & 255,
-                         j=(w >> 16) & 255, k=(w >> 24) & 255, fetch=int(r["fetch"]),
+        rows.append(dict(slot=int(r["slot"]), type=w & 7, part=(w >> 3) & 15, fine=(w >> 7) & 1, i=(w >> 8) & 63,
+                         j=(w >> 16) & 63, k=(w >> 24) & 63,  # (bits 14-15, 22: a K batch's length − 1)
+                         len=1 + ((w >> 14) & 3) + 4 * ((w >> 22) & 1), fetch=int(r["fetch"]),
                          ready=int(r["ready"]), done=int(r["done"]), wg=int(r["wg"]),
                          xcc=int(r["xcc"])))
     t0 = min(r["fetch"] for r in rows)
