@@ -163,6 +163,15 @@ enum {
                              other summation order within a batch; for a given value the bits do
                              not depend on the queue order, the workgroup count or the load
                              group. */
+  GPS_OPT_DAG_TILE_FORM = 30, /* persistent factorisation: minlen | d << 4 — a K batch (option 29)
+                             of an off-diagonal tile with at least minlen (1..8) terms, whose last
+                             term ends at least d (0..15) tile columns short of the column where
+                             the tile is consumed, runs as ONE task on one workgroup, each wave a
+                             64×64 block, instead of four 32-row strips.  0: strips only, the
+                             queue of before word for word.  Acts only in blocks that have
+                             batches.  Default 2 | 2 << 4.  For a given option 29 the bits are those of
+                             the strips (same K range and per-element product chain; DESIGN
+                             §29). */
 };
 int gps_ctx_set_option(gps_ctx* ctx, int key, int value);
 
@@ -192,6 +201,10 @@ int gps_dag_task_list(int T, int flags, uint32_t* out, int cap);
  * bits 14-15 (low two) and 22 (high), k (UPD) resp. j (UPDX) naming the batch's first term.
  * kb = 1 gives gps_dag_task_list's words exactly. */
 int gps_dag_task_list_ex(int T, int flags, int kb, int kg, uint32_t* out, int cap);
+/* The same with the tile form (GPS_OPT_DAG_TILE_FORM's value tf: 0, or minlen | d << 4): a batch
+ * in tile form is one word with bit 23 set and part 0, standing for the four strips of its tile.
+ * tf = 0 gives gps_dag_task_list_ex's words exactly. */
+int gps_dag_task_list_tf(int T, int flags, int kb, int kg, int tf, uint32_t* out, int cap);
 
 /* Diagnostics: ONE internal FP64 GEMM launch (csrc/kernels_gemm.hip's launch_gemm, through the
  * same gemm() every production caller uses, on the context's main stream with that stream's

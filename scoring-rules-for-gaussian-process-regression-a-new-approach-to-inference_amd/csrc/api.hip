@@ -288,8 +288,8 @@ int fitc_rowsq_dep(gps_ctx* ctx, const double* L, int* sig, int64_t ncols, int m
 }
 
 // the task list of an nb-tile persistent block under the context's options
-int dag_list_key(const gps_ctx* ctx, int64_t nb) {
-  return (int)(3 * nb + ctx->dag_order) << 8 | dag_kg(ctx, nb) << 4 | dag_kb(ctx, nb);
+int dag_list_key(const gps_ctx* ctx, int64_t nb) {  // 8 + 2 + 4 + 8 bits
+  return ((int)(3 * nb + ctx->dag_order) << 8 | dag_kg(ctx, nb) << 4 | dag_kb(ctx, nb)) << 8 | dag_tf(ctx, nb);
 }
 // the K batches of an nb-tile block's task list (GPS_OPT_DAG_KBATCH): at most B terms, the last g
 // single; with bit 8 set only in blocks above GPS_OPT_DAG_TILES — smaller ones are bound by
@@ -299,6 +299,10 @@ int dag_kb(const gps_ctx* ctx, int64_t nb) {
   return std::max(1, ctx->dag_kbatch & 15);
 }
 int dag_kg(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->dag_kbatch >> 4 & 3 : 0; }
+// the batches of an nb-tile block that run in tile form (GPS_OPT_DAG_TILE_FORM): only where there
+// are batches — the single-term lists (the FITC blocks, every block up to GPS_OPT_DAG_TILES under
+// the default) stay word for word what they were
+int dag_tf(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->dag_tile_form : 0; }
 
 // a block of nb 128-tiles goes to the persistent factorisation (GPS_OPT_DAG); the full GP's
 // factorisation has a cap of its own (GPS_OPT_DAG_TILES_FULL)
@@ -540,7 +544,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
   for (int T : dsizes) {
     const int lk = dag_list_key(ctx, T);
     if (ctx->dag_lists.count(lk)) continue;
-    const std::vector<uint32_t> tl = dag_task_list(T, ctx->dag_order, true, dag_kb(ctx, T), dag_kg(ctx, T));
+    const std::vector<uint32_t> tl = dag_task_list(T, ctx->dag_order, true, dag_kb(ctx, T), dag_kg(ctx, T), dag_tf(ctx, T));
     auto& e = ctx->dag_lists[lk];
     HIPCHK(ensure(ctx, e.first, tl.size() * 4));
     // (stream-ordered, never the legacy stream: another context of this process may be
@@ -580,7 +584,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
       pre ? (uintptr_t)ctx->Knm.p : 0, pre ? (uintptr_t)ctx->fslab.p : 0,
       pre ? (uintptr_t)ctx->fn_pad : 0, pre ? (uintptr_t)ctx->m_pad : 0, pre ? (uintptr_t)ctx->pre.sig : 0,
       (uintptr_t)ctx->dag, (uintptr_t)ctx->dag_tiles,
-      (uintptr_t)(ctx->dag_full ? ctx->dag_tiles_full : 0), (uintptr_t)ctx->dag_kbatch, (uintptr_t)ctx->dag_group, (uintptr_t)ctx->dag_wgs, (uintptr_t)ctx->dag_half,
+      (uintptr_t)(ctx->dag_full ? ctx->dag_tiles_full : 0), (uintptr_t)ctx->dag_kbatch, (uintptr_t)ctx->dag_tile_form, (uintptr_t)ctx->dag_group, (uintptr_t)ctx->dag_wgs, (uintptr_t)ctx->dag_half,
       (uintptr_t)ctx->dag_cnt.p, (uintptr_t)ctx->sk_cnt.p, (uintptr_t)ctx->dag_sig};
   for (int T : dsizes) key.push_back((uintptr_t)ctx->dag_lists[dag_list_key(ctx, T)].first.p);  // the task lists
   for (auto& g : ctx->pgraphs)
@@ -855,6 +859,11 @@ int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
              "GPS_OPT_DAG_KBATCH must be B | g << 4 [| 256] with B in 0..8 and g in 0..3");
       ctx->dag_kbatch = (value & 15) < 2 ? 0 : value;
       return 0;
+    case GPS_OPT_DAG_TILE_FORM:
+      ARGCHK(value >= 0 && (value & 15) <= 8 && (value >> 8) == 0 && ((value & 15) || !value),
+             "GPS_OPT_DAG_TILE_FORM must be 0 or minlen | d << 4 with minlen in 1..8 and d in 0..15");
+      ctx->dag_tile_form = value;
+      return 0;
     default: return fail(ctx, -1, "unknown option");
   }
 }
@@ -888,10 +897,15 @@ int gps_dag_task_list(int T, int flags, uint32_t* out, int cap) {
 }
 
 int gps_dag_task_list_ex(int T, int flags, int kb, int kg, uint32_t* out, int cap) {
-  if (T < 2 || T > 64 || cap < 0 || (cap > 0 && !out) || (flags & ~13) || kb < 1 || kb > 8 || kg < 0 || kg > 3)
+  return gps_dag_task_list_tf(T, flags, kb, kg, 0, out, cap);
+}
+
+int gps_dag_task_list_tf(int T, int flags, int kb, int kg, int tf, uint32_t* out, int cap) {
+  if (T < 2 || T > 64 || cap < 0 || (cap > 0 && !out) || (flags & ~13) || kb < 1 || kb > 8 || kg < 0 || kg > 3 ||
+      tf < 0 || (tf >> 8) || (tf & 15) > 8 || (tf && !(tf & 15)))
     return fail(nullptr, -1, "bad arguments");
   const std::vector<uint32_t> tl = dag_task_list(T, (flags >> 2 & 3) == 0 ? 1 : (flags >> 2 & 3) == 3 ? 0 : flags >> 2 & 3,
-                                                 (flags & 1) != 0, kb, kg);
+                                                 (flags & 1) != 0, kb, kg, tf);
   for (int i = 0; i < cap && i < (int)tl.size(); ++i) out[i] = tl[i];
   return (int)tl.size();
 }

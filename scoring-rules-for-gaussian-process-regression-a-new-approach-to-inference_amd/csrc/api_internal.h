@@ -136,12 +136,13 @@ struct gps_ctx {
   int dag_tiles_full = 40;             // GPS_OPT_DAG_TILES_FULL: the full GP's cap (0: dag_tiles)
   int dag_kbatch = 8 | 256;            // GPS_OPT_DAG_KBATCH: B | g << 4 | 256 (B < 2: every term a
                                        // task; 256: in blocks above dag_tiles only)
+  int dag_tile_form = 2 | 2 << 4;      // GPS_OPT_DAG_TILE_FORM: minlen | d << 4 (0: strips only)
   bool dag_full = false;               // this factorisation is full_fit_core's (dag_tiles_full applies)
   bool dag_half = false;               // this factorisation leaves half the CUs to a side stream
   bool fitc_dep = true;                // GPS_OPT_FITC_DEP: the q row norms behind Lm's factorisation
   int* dag_sig = nullptr;              // the top-level persistent launch's row signals (kSig*), if any
   DBuf dsig;                           // the FITC signal block of Lm's factorisation (kSigInts ints)
-  std::map<int, std::pair<DBuf, int>> dag_lists;  // per dag_list_key (T, order, K batches): device task list, length
+  std::map<int, std::pair<DBuf, int>> dag_lists;  // per dag_list_key (T, order, K batches, tile form): device task list, length
   // factor buffers (L⁻¹, L) known to hold zeros for a padded size: potrf_inv writes their lower
   // triangles only and refuses a buffer without an entry here (zero_factor); freeing or growing
   // a buffer forgets its entries (the zero-upper contract is checked, not assumed)
@@ -332,6 +333,7 @@ int fitc_rowsq_cols(gps_ctx* ctx, const double* Lx, int64_t c0, int64_t c1, hipS
 int fitc_rowsq_dep(gps_ctx* ctx, const double* L, int* sig, int64_t ncols, int mode,
                    hipStream_t st, int64_t nb_dag);
 int dag_list_key(const gps_ctx* ctx, int64_t nb);
+int dag_tf(const gps_ctx* ctx, int64_t nb);
 int dag_kb(const gps_ctx* ctx, int64_t nb);
 int dag_kg(const gps_ctx* ctx, int64_t nb);
 bool dag_block(const gps_ctx* ctx, int64_t nb);

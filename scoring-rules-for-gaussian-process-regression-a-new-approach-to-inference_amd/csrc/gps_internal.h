@@ -455,8 +455,10 @@ struct DagParams {
 };
 hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s);
 // kb: UPD / UPDX terms of one tile in batches of at most kb (1: every term its own task, the
-// list of before); kg: the last kg terms of every tile stay single tasks
-std::vector<uint32_t> dag_task_list(int T, int order = 1, bool fine = true, int kb = 1, int kg = 0);
+// list of before); kg: the last kg terms of every tile stay single tasks; tf: the batches that
+// run in tile form (GPS_OPT_DAG_TILE_FORM's value, 0: none)
+std::vector<uint32_t> dag_task_list(int T, int order = 1, bool fine = true, int kb = 1, int kg = 0,
+                                    int tf = 0);
 inline int64_t dag_cnt_ints(int T) { return (16 + 2 * (int64_t)T * T + 63) / 64 * 64; }
 
 // y[i] = sum_k L[i][k] x[k] over the tile-lower part (rows < n_pad)

@@ -630,6 +630,125 @@ __device__ __forceinline__ void run_strip(const Strip& s) {
       }
 }
 
+// Tile form of a batched UPD / UPDX task: the whole 128×128 tile on one workgroup,
+// each wave a 64×64 block.  A 16-deep chunk is then 32 doubles per lane for 64 MFMAs (two per
+// loaded double, a strip's 32×32 block has one), so three one-chunk buffers — the registers of
+// the strip's two groups of three — keep two chunks (128 MFMAs) in flight ahead of the one being
+// multiplied.  The operand fragments, their `sc1` loads and the MFMA chain of every output
+// element (chunks ascending, kk ascending within a chunk) are wave_gemm32's: the same bits.
+// one wave: acc = A (64 rows, k in [kb, ke), lda) · B, B stored [k][j] (BT = false, 64 columns)
+// or [j][k] (BT = true, 64 rows)
+template <bool BT>
+__device__ __forceinline__ void wave_gemm64(const double* Ap, int64_t lda, const double* Bp,
+                                            int64_t ldb, int kb, int ke, d4 (&acc)[4][4]) {
+  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+  const __amdgpu_buffer_rsrc_t ra = rsrc(Ap, (uint32_t)(64 * lda * 8));
+  const __amdgpu_buffer_rsrc_t rb = rsrc(Bp, (uint32_t)((BT ? 64 : ke > 128 ? ke : 128) * ldb * 8));
+  struct Frag { double a[4][4], b[4][4]; };  // [16-block][k step]
+  const int nc = (ke - kb) / 16;
+  const uint32_t oa0 = (uint32_t)(((int64_t)r * lda + kb + 4 * g) * 8), sa = (uint32_t)(16 * lda * 8);
+  const uint32_t ob0 = BT ? (uint32_t)(((int64_t)r * ldb + kb + 4 * g) * 8)
+                          : (uint32_t)(((int64_t)(kb + 4 * g) * ldb + r) * 8);
+  const uint32_t sb = BT ? (uint32_t)(16 * ldb * 8) : (uint32_t)(ldb * 8);
+  auto load = [&](int c, Frag& f) {
+    const uint32_t oa = oa0 + 128u * (uint32_t)c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const dv2 a0 = ld128(ra, oa + i * sa), a1 = ld128(ra, oa + i * sa + 16);
+      f.a[i][0] = a0.x; f.a[i][1] = a0.y; f.a[i][2] = a1.x; f.a[i][3] = a1.y;
+    }
+    if constexpr (BT) {
+      const uint32_t ob = ob0 + 128u * (uint32_t)c;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const dv2 b0 = ld128(rb, ob + i * sb), b1 = ld128(rb, ob + i * sb + 16);
+        f.b[i][0] = b0.x; f.b[i][1] = b0.y; f.b[i][2] = b1.x; f.b[i][3] = b1.y;
+      }
+    } else {
+      const uint32_t ob = ob0 + 16u * (uint32_t)c * sb;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f.b[i][e] = ld64(rb, ob + e * sb + 128u * i);
+    }
+  };
+  auto mma = [&](const Frag& f) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.a[i][kk], f.b[j][kk], acc[i][j], 0, 0, 0);
+  };
+  // nc ≥ 4 (K ≥ 128, the clipped first term starts at 0 or 64).  The steady-state loop has no
+  // conditional load: a load under a branch makes the compiler's vmcnt at the join the count that
+  // is right on the path WITHOUT the load, which drains the chunks in flight on the path with it
+  // (the first build: vmcnt(16), then vmcnt(0), where 32 were meant).
+  Frag f0, f1, f2;
+  load(0, f0);
+  load(1, f1);
+  int c = 0;
+  for (; c + 5 <= nc; c += 3) {
+    load(c + 2, f2);
+    mma(f0);
+    load(c + 3, f0);
+    mma(f1);
+    load(c + 4, f1);
+    mma(f2);
+  }
+  const int rem = nc - c;  // 2..4 chunks left, the first two in f0, f1 (wave-uniform tests)
+  if (rem >= 3) load(c + 2, f2);
+  mma(f0);
+  if (rem == 4) load(c + 3, f0);
+  mma(f1);
+  if (rem >= 3) mma(f2);
+  if (rem == 4) mma(f0);
+}
+
+struct Tile {           // one wave's 64×64 block of a tile-form task
+  const double* A; int64_t lda;
+  const double* B; int64_t ldb; int bt;
+  double* C; int64_t ldc;
+  double alpha, beta;
+  int kb, ke;
+};
+
+// all four waves: the product, then C's read-modify-write in the operand buffers' registers
+// (one round trip per task, after the K loop: nothing else writes this tile while the task runs
+// — its earlier terms are in, which the task polled, and its later ones wait for this arrival),
+// alpha·acc + beta·C formed as run_strip forms it, write-through stores
+__device__ __forceinline__ void run_tile(const Tile& s) {
+  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+  const __amdgpu_buffer_rsrc_t rc = rsrc(s.C, (uint32_t)(64 * s.ldc * 8));
+  d4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+  if (s.bt) wave_gemm64<true>(s.A, s.lda, s.B, s.ldb, s.kb, s.ke, acc);
+  else wave_gemm64<false>(s.A, s.lda, s.B, s.ldb, s.kb, s.ke, acc);
+  const uint32_t oc = (uint32_t)(((int64_t)g * s.ldc + r) * 8), sc = (uint32_t)(4 * s.ldc * 8);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {  // a 16-row block at a time: 16 loads in flight, then 16 stores
+    double cold[4][4];
+    if (s.beta != 0.0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cold[j][e] = ld64(rc, oc + (4 * i + e) * sc + 128u * j);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        double v = s.alpha * acc[i][j][e];
+        if (s.beta != 0.0) v = fma(s.beta, cold[j][e], v);
+        st64(rc, oc + (4 * i + e) * sc + 128u * j, v);
+      }
+  }
+}
+
 // Fine parts of the two tile tasks on the leaf chain, TRSM(k+1,k) and UPD(k+1,k+1,k) (round 4):
 // LEAF(k) -> TRSM(k+1,k) -> UPD(k+1,k+1,k) -> LEAF(k+1) ran 9.5 + 11.7 µs of strip tasks per
 // 128 columns (profiles/r3_dag_trace20_rank.txt), each wave a 32×32 block with K = 128: 128
@@ -902,6 +1021,32 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
         out = acnt + ti * T + tj;
       }
       run_fine(f);
+    } else if (w >> 23 & 1) {  // tile form of a batched UPD / UPDX (off-diagonal tiles only)
+      Tile tl;
+      const int64_t R = 128 * (int64_t)ti + 64 * (wave >> 1), J = 128 * (int64_t)tj,
+                    K = 128 * (int64_t)tk, wc = 64 * (wave & 1);
+      if (type == 2) {  // UPD(i, j, k ..): A_ij −= L_i,k.. · L_j,k..ᵀ
+        tl.A = p.A + R * lda + K; tl.lda = lda;
+        tl.B = p.A + (J + wc) * lda + K; tl.ldb = lda; tl.bt = 1;
+        tl.C = p.A + R * lda + J + wc; tl.ldc = lda;
+        tl.alpha = -1.0; tl.beta = 1.0; tl.kb = 0;
+        out = acnt + ti * T + tj;
+      } else {  // UPDX(i, k, j ..): S_ik (+)= L_i,j.. · X_j..,k
+        tl.A = p.A + R * lda + J; tl.lda = lda;
+        tl.B = p.Linv + J * ldl + K + wc; tl.ldb = ldl; tl.bt = 0;
+        tl.C = p.Linv + R * ldl + K + wc; tl.ldc = ldl;
+        tl.alpha = 1.0; tl.beta = tj == tk ? 0.0 : 1.0;
+        // the clipped first term: X_kk is lower triangular, so a strip's wave starts at its own
+        // 32 columns; here from the wave's first column — for its upper 32 columns that adds the
+        // products with four 16-blocks above X_kk's block diagonal (never written, zeroed by
+        // every caller: see the end of leaf_body) ahead of the strip's chain: fma(a, ±0, +0) = +0
+        // for every finite a, the value the strip's chain starts from, so the bits are the strip's
+        tl.kb = tj == tk ? (int)wc : 0;
+        out = xcnt + ti * T + tk;
+      }
+      tl.ke = 128 * len;
+      inc = len * U;  // the four strips' worth: the counters keep meaning "U per applied term"
+      run_tile(tl);
     } else {
       inc = U / NP;
       Strip st;
@@ -997,8 +1142,8 @@ hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s) {
   if ((p.lda & 1) || (p.ldl & 1) || (p.Lout && (p.ldlo & 1)) || p.T < 1 || p.T > 64 || nwg < 1 ||
       !p.tasks || !p.cnt || p.ntasks < 1 || p.kbatch < 1 || p.kbatch > 8)
     return hipErrorInvalidValue;
-  // every strip's buffer descriptor spans at most 128 rows of its matrix, 128·kbatch for a
-  // batched UPDX's B operand (32-bit offsets)
+  // every strip's buffer descriptor spans at most 128 rows of its matrix (a tile-form wave's: 64),
+  // 128·kbatch for a batched UPDX's B operand in either form (32-bit offsets)
   if ((int64_t)128 * p.kbatch * std::max(p.lda, p.ldl) * 8 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
   auto k = p.trace ? (p.group == 2 ? dag::potrf_dag_kernel<true, 2>
                                     : p.group == 3 ? dag::potrf_dag_kernel<true, 3> : dag::potrf_dag_kernel<true, 4>)
@@ -1025,14 +1170,26 @@ hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s) {
 // profiles/r5_prune_split_chain.diff.)
 // Word: type | part << 3 | fine << 7 | i << 8 | j << 16 | k << 24, i, j, k in 6 bits each; the K
 // batch length − 1 of an UPD / UPDX task (0..7) in bits 14-15 (low) and 22 (high),
-// k resp. j its first term — length field 0 is the single-term task of before.
-// order 1's weights, µs: LEAF, fine part, TRSM, UPD, UPDX, FIN strips, hand-off (tools/dag_bench
-// overrides them for sweeps; the library never writes them)
-double g_dag_weights[7] = {35.0, 6.0, 9.7, 11.7, 11.2, 9.3, 2.5};
+// k resp. j its first term — length field 0 is the single-term task of before.  Bit 23: the tile
+// form of a batch (one word for the whole tile, part 0).
+// order 1's weights, µs: LEAF, fine part, TRSM, UPD, UPDX, FIN strips, hand-off, and the factor
+// of a tile-form task over a strip of its batch (tools/dag_bench overrides them for sweeps; the
+// library never writes them)
+double g_dag_weights[8] = {35.0, 6.0, 9.7, 11.7, 11.2, 9.3, 2.5, 2.0};
 
-std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg) {
+std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg, int tf) {
   // len: the K batch of an UPD / UPDX task (terms k .. k + len − 1, resp. j .. j + len − 1)
-  struct Task { int type, i, j, k, len; std::vector<int> deps; double est = 0.0, rank = 0.0; };
+  struct Task { int type, i, j, k, len; std::vector<int> deps; double est = 0.0, rank = 0.0; int tile = 0; };
+  // Tile form (GPS_OPT_DAG_TILE_FORM, tf = minlen | d << 4): a batch of an
+  // off-diagonal tile with at least minlen terms whose last term ends at least d tile columns
+  // short of where the tile is consumed (UPD(i, j, k0..k1−1): j − k1 ≥ d, the tile feeds
+  // TRSM(i, j); UPDX(i, k, j0..j1−1): i − j1 ≥ d, it feeds FIN(i, k)) is ONE queue word, the whole
+  // tile on one workgroup — a function of (T, kb, kg, tf, the tile, the batch) alone.
+  const int tf_min = tf & 15, tf_d = tf >> 4 & 15;
+  auto tile_form = [&](const Task& t) {
+    if (!tf_min || (t.type != 2 && t.type != 3) || t.len < tf_min) return false;
+    return t.type == 2 ? t.i > t.j && t.j - (t.k + t.len) >= tf_d : t.i - (t.j + t.len) >= tf_d;
+  };
   auto is_fine = [&](const Task& t) {
     return fine && ((t.type == 1 && t.i == t.k + 1) || (t.type == 2 && t.i == t.k + 1 && t.j == t.i));
   };
@@ -1052,6 +1209,7 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg)
   auto add = [&](int type, int i, int j, int k, int len, std::vector<int> deps) {
     Task t;
     t.type = type; t.i = i; t.j = j; t.k = k; t.len = len;
+    t.tile = tile_form(t);
     for (int d : deps)
       if (d >= 0) t.deps.push_back(d);
     tk.push_back(t);
@@ -1098,12 +1256,12 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg)
   for (int t = 0; t < n; ++t)
     for (int d : tk[t].deps) { succ[d].push_back(t); ++indeg[t]; }
   if (order == 0) {
-    auto dur = [&](const Task& t) { return t.type == 0 ? 36.0 : 4.0 * t.len; };
+    auto dur = [&](const Task& t) { return t.type == 0 ? 36.0 : 4.0 * t.len * (t.tile ? 2.0 : 1.0); };
     for (int t = 0; t < n; ++t)  // generation order is topological
       for (int d : tk[t].deps) tk[t].est = std::max(tk[t].est, tk[d].est + dur(tk[d]) + 3.0);
   } else if (order == 2) {  // round 3's weights
     auto dur = [&](const Task& t) {
-      return t.type == 0 ? 38.0 : is_fine(t) ? 4.0 : 9.0 * t.len;
+      return t.type == 0 ? 38.0 : is_fine(t) ? 4.0 : 9.0 * t.len * (t.tile ? 2.0 : 1.0);
     };
     for (int t = n - 1; t >= 0; --t) {
       double m = 0.0;
@@ -1118,11 +1276,12 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg)
     const double* w = g_dag_weights;
     auto dur = [&](const Task& t) {
       if (is_fine(t)) return w[1];
+      const double tw = t.tile ? w[7] : 1.0;  // (a tile-form task runs its four strips' work)
       switch (t.type) {
         case 0: return w[0];
         case 1: return w[2];
-        case 2: return w[3] * t.len;  // (a K batch weighs as its K)
-        case 3: return w[4] * t.len;
+        case 2: return w[3] * t.len * tw;  // (a K batch weighs as its K)
+        case 3: return w[4] * t.len * tw;
         default: return w[5];
       }
     };
@@ -1143,11 +1302,11 @@ std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg)
     ready.pop();
     const Task& x = tk[t];
     const bool f = is_fine(x);
-    const int parts = x.type == 0 ? 1 : !f ? dag::NP : x.type == 1 ? dag::NPF_TRSM : dag::NPF_UPD;
+    const int parts = x.type == 0 || x.tile ? 1 : !f ? dag::NP : x.type == 1 ? dag::NPF_TRSM : dag::NPF_UPD;
     for (int q = 0; q < parts; ++q)
       out.push_back((uint32_t)x.type | (uint32_t)q << 3 | (uint32_t)f << 7 | (uint32_t)x.i << 8 |
                     (uint32_t)((x.len - 1) & 3) << 14 | (uint32_t)x.j << 16 |
-                    (uint32_t)((x.len - 1) >> 2) << 22 | (uint32_t)x.k << 24);
+                    (uint32_t)((x.len - 1) >> 2) << 22 | (uint32_t)x.tile << 23 | (uint32_t)x.k << 24);
     for (int s2 : succ[t])
       if (!--indeg[s2]) ready.push({tk[s2].est, s2});
   }

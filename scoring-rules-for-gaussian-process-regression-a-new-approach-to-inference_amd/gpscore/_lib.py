@@ -34,10 +34,12 @@ GPS_OPT_SLAB_XCD = 26
 GPS_OPT_FITC_DEP = 27
 GPS_OPT_DAG_TILES_FULL = 28
 GPS_OPT_DAG_KBATCH = 29
+GPS_OPT_DAG_TILE_FORM = 30
 # the library's defaults of those two (api_internal.h): 40-tile blocks in the full GP's fit, and
 # batches of 8 K tiles in the blocks above GPS_OPT_DAG_TILES (bit 8 of the batch option)
 DAG_TILES_FULL_DEFAULT = 40
 DAG_KBATCH_DEFAULT = 8 | 256
+DAG_TILE_FORM_DEFAULT = 2 | 2 << 4  # minlen | d << 4; 0: strips only
 GPS_OPT_AR_CHUNKS = 15
 OBJ_NAMES = ("nlml", "loo_crps", "loo_logs", "logdet", "quad")
 SURFACE_NAMES = ("loo_crps", "insample_crps", "nlml", "loo_logs")
@@ -92,6 +94,7 @@ SIGNATURES = {
     "gps_ctx_stats": (_c_int, [_c_vp, _c_vp, _c_int]),
     "gps_dag_task_list": (_c_int, [_c_int, _c_int, _c_vp, _c_int]),
     "gps_dag_task_list_ex": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_vp, _c_int]),
+    "gps_dag_task_list_tf": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_int]),
     "gps_gemm_diag_check": (_c_int, [ctypes.POINTER(GemmDesc), _c_int, _c_int, _c_int, _PI, _c_int,
                                      _c_int]),
     "gps_gemm_schedule": (_c_i64, [ctypes.POINTER(GemmDesc), _PI, _c_int, _c_int, _PI, _PI, _c_i64]),

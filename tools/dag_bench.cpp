@@ -3,11 +3,14 @@
 // (L·Lᵀ = A and L⁻¹·L = I on random entries), and one traced launch whose per-slot timestamps
 // go to a CSV for tools/dag_trace.py (critical path, hand-off latencies, per-type durations).
 //   dag_bench [T=20] [nwg=256] [trace.csv|-] [reps=20] [group=3] [order=1] [fine=1] [weights|-]
-//             [B=1] [g=0]
-// B, g: the K batches of the UPD / UPDX tasks (GPS_OPT_DAG_KBATCH).  A traced launch always runs:
+//             [B=1] [g=0] [form=0]
+// B, g: the K batches of the UPD / UPDX tasks (GPS_OPT_DAG_KBATCH); form: the batches that run in
+// tile form (GPS_OPT_DAG_TILE_FORM's value, minlen | d << 4; its rank factor is an eighth weight).
+// A traced launch always runs:
 // the bulk strip-task rate printed beside the block time is the flops of the UPD / UPDX strip
 // tasks over their fetch-to-done time, summed over the workgroups (what the off-chain tasks
-// sustain, waits included), with the mean fetch-to-done and ready-to-done time per strip task.
+// sustain, waits included), with the mean fetch-to-done and ready-to-done time per strip task;
+// the tile-form tasks are reported on a line of their own (count, times, rate while they run).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -32,11 +35,13 @@ int main(int argc, char** argv) {
   const int fine = argc > 7 ? atoi(argv[7]) : 1;
   const int kb = argc > 9 ? atoi(argv[9]) : 1;
   const int kg = argc > 10 ? atoi(argv[10]) : 0;
+  const int tf = argc > 11 ? atoi(argv[11]) : 0;
   if (kb < 1 || kb > 8 || kg < 0 || kg > 3) { fprintf(stderr, "B in 1..8, g in 0..3\n"); return 2; }
+  if (tf < 0 || tf > 255 || (tf & 15) > 8 || (tf && !(tf & 15))) { fprintf(stderr, "form: 0 or minlen (1..8) | d << 4\n"); return 2; }
   if (argc > 8 && argv[8][0] != '-') {  // order 1's weights: LEAF,fine,TRSM,UPD,UPDX,FIN,hand-off
     double* w = gps::g_dag_weights;
-    if (sscanf(argv[8], "%lf,%lf,%lf,%lf,%lf,%lf,%lf", w, w + 1, w + 2, w + 3, w + 4, w + 5, w + 6) != 7) {
-      fprintf(stderr, "weights: 7 comma-separated numbers\n");
+    if (sscanf(argv[8], "%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf", w, w + 1, w + 2, w + 3, w + 4, w + 5, w + 6, w + 7) < 7) {
+      fprintf(stderr, "weights: 7 or 8 comma-separated numbers\n");
       return 2;
     }
   }
@@ -52,7 +57,7 @@ int main(int argc, char** argv) {
       for (int k = 0; k < d; ++k) { const double t = X[i * d + k] - X[j * d + k]; s += t * t; }
       h[(size_t)i * n + j] = exp(-0.25 * s) + (i == j ? 0.05 : 0.0);
     }
-  const std::vector<uint32_t> tl = dag_task_list(T, order, fine != 0, kb, kg);
+  const std::vector<uint32_t> tl = dag_task_list(T, order, fine != 0, kb, kg, tf);
   const int nt = (int)tl.size();
   double *A0, *A, *Li, *ld;
   int *info, *cnt;
@@ -123,7 +128,7 @@ int main(int argc, char** argv) {
   double lsum = 0;
   for (double x : gld) lsum += x;
   const double fl = 2.0 * n * (double)n * n / 3.0;
-  printf("group=%d order=%d fine=%d w=%s B=%d g=%d ", group, order, fine, argc > 8 ? argv[8] : "-", kb, kg);
+  printf("group=%d order=%d fine=%d w=%s B=%d g=%d form=%d ", group, order, fine, argc > 8 ? argv[8] : "-", kb, kg, tf);
   printf("T=%d n=%d nwg=%d tasks=%d: median %.3f ms (min %.3f, max %.3f) = %.1f us/tile, %.2f TF/s; "
          "max|XAX^T - I| %.2e over 24 samples, sum log L_ii %.6f\n",
          T, n, nwg, nt, ts[ts.size() / 2], ts[0], ts.back(), 1e3 * ts[ts.size() / 2] / T,
@@ -133,13 +138,20 @@ int main(int argc, char** argv) {
     launch(true, &ms);
     std::vector<unsigned long long> tr((size_t)nt * 4);
     CK(hipMemcpy(tr.data(), trace, (size_t)nt * 32, hipMemcpyDeviceToHost));
-    double bflop = 0.0, bticks = 0.0, rticks = 0.0;
-    long nb = 0;
+    double bflop = 0.0, bticks = 0.0, rticks = 0.0, tflop = 0.0, tticks = 0.0, trticks = 0.0;
+    long nb = 0, ntf = 0;
     for (int t = 0; t < nt; ++t) {
       const uint32_t w = tl[t];
       const int type = w & 7, part = (w >> 3) & 15, fn = (w >> 7) & 1, i = (w >> 8) & 63, j = (w >> 16) & 63,
                 k = (w >> 24) & 63, len = 1 + ((w >> 14) & 3) + 4 * ((w >> 22) & 1);
       if (fn || (type != 2 && type != 3)) continue;
+      if (w >> 23 & 1) {  // tile form: four 64×64 blocks, the clipped first UPDX term from 64·(w & 1)
+        tflop += 4.0 * 2.0 * 64 * 64 * 128.0 * len - (type == 3 && j == k ? 2.0 * 2.0 * 64 * 64 * 64.0 : 0.0);
+        tticks += (double)(tr[4 * t + 2] - tr[4 * t]);
+        trticks += (double)(tr[4 * t + 2] - tr[4 * t + 1]);
+        ++ntf;
+        continue;
+      }
       // 32×32 blocks the strip's four waves run: UPD on a diagonal tile the lower ones only; the
       // first UPDX term starts at the wave's own column (X_kk lower)
       double f = 0.0;
@@ -156,6 +168,11 @@ int main(int argc, char** argv) {
     printf("bulk strip tasks (traced launch %.3f ms): %ld UPD/UPDX strips, %.2f us fetch-to-done, %.2f us "
            "ready-to-done, %.1f TF/s over %d workgroups\n", ms, nb, bticks / nb * 1e-2, rticks / nb * 1e-2,
            bflop / (bticks * 1e-8) * nwg / 1e12, nwg);
+    if (ntf)
+      printf("bulk tile-form tasks: %ld UPD/UPDX tiles, %.2f us fetch-to-done, %.2f us ready-to-done, %.1f TF/s "
+             "while running (ready-to-done) and %.1f TF/s fetch-to-done over %d workgroups\n", ntf,
+             tticks / ntf * 1e-2, trticks / ntf * 1e-2, tflop / (trticks * 1e-8) * nwg / 1e12,
+             tflop / (tticks * 1e-8) * nwg / 1e12, nwg);
     if (!tpath) return err < 1e-8 ? 0 : 3;
     FILE* f = fopen(tpath, "w");
     fprintf(f, "slot,word,fetch,ready,done,wg,xcc\n");
