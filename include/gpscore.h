@@ -63,7 +63,8 @@ enum {
  * diagnostics gps_grad_terms_diag / gps_grad_contract_diag / gps_fitc_contract_diag
  * and gps_full_grad_tall / gps_full_train_tall, their block-LOO siblings
  * gps_full_blockloo_grad_tall / gps_full_blockloo_train_tall and
- * gps_fitc_blockloo_grad_tall / gps_fitc_blockloo_train_tall.
+ * gps_fitc_blockloo_grad_tall / gps_fitc_blockloo_train_tall, and the vector-layer
+ * diagnostic gps_vec_diag.
  * The binding refuses a mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -319,6 +320,52 @@ int gps_fitc_contract_diag(gps_ctx* ctx, int64_t nr, int64_t nc, int64_t nc_pad,
                            int nt, const double* const* R, const int64_t* ldr, const double* coef,
                            const double* const* rs, const double* pc, const double* const* pv,
                            const double* const* qv, double* out, double* zout);
+
+/* Diagnostics: the vector layer's kernels (csrc/kernels_vec.hip) one production launch_* call at
+ * a time on host arrays (tests/test_gpu_vec.py).  The call judges its arguments before
+ * anything touches the device (-1 with the reason in gps_last_error; the launchers' own refusals
+ * — odd cols, odd ld, crows < 1, n outside 1..64 for the local sum, the transposed trmv — are
+ * among them), uploads, and copies the outputs back.  On the device everything the kernel must
+ * write and everything it must not read is NaN beforehand: the strict-upper 128-tiles of the
+ * lower forms, the row gaps where ld exceeds the row length, one slab past the nslab real ones,
+ * the vectors past their real length, and the outputs.  An optional operand that is NULL here
+ * is NULL in the launch.  dims: 8 integers, scal: 2 doubles, in / out: 8 pointer slots each
+ * (unused entries are not read).  Matrices are dense row-major on the host ([rows][cols]); the
+ * device copy has the row stride given in dims.  With n_pad = n rounded up to 128:
+ *   which  launcher                 dims                              in -> out
+ *   0  launch_gemv_full / _lower /  {mode 0 full 1 lower 2 trmv,      {M, x} -> {y [rows]}
+ *      launch_trmv_lower             rows, cols, ldm, trans}
+ *   1  launch_colred                {rows, cols, ldm, lower, crows}   {M, w|NULL, rowscale|NULL}
+ *                                                                      -> {s1|NULL, s2|NULL}
+ *   2  launch_colred_partials       {rows, cols, ldm, lower}          {M, w} -> {slab [2][nchunk]
+ *                                                                      [cols], count [1]}
+ *   3  launch_slab_sum              {nslab, len, ld}                  {slab [nslab][len],
+ *                                                                      init|NULL} -> {out [len]}
+ *   4  launch_sym_slab_sum          {nslab, M, stride}                {slab [nslab][M*M],
+ *                                                                      base|NULL} -> {dst [M*M]}
+ *   5  launch_sym_pack (rows [r0,   {nslab, M, stride, m, r0, r1,     same -> {packed [m(m+1)/2]
+ *      r1)), then launch_sym_unpack  unpack, full}                     (uploaded first: what the
+ *      if unpack                                                       pack leaves alone stays),
+ *                                                                      dst [M*M] if unpack}
+ *   6  launch_full_loo              {n, nslab, ld}                    {y [n], slab1, slab2
+ *                                                                      [nslab][n_pad], beta,
+ *      logdiag [n_pad]} -> {alpha, dinv, mu_loo, var_loo [n_pad], obj [5], sums [4]}
+ *   7  launch_fitc_lambda           {n, n_pad, nslab, ld}; scal       {slab [nslab][n_pad], y [n]}
+ *                                    {sf2, sn2}                        -> {q, lam, inv_lam, ys
+ *                                                                      [n_pad], sums [2]}
+ *   8  launch_fitc_loo              {n, n_pad, nslab, ld}             {y, lam [n], slab [nslab]
+ *      [n_pad], g [n]} -> {r, mu_loo, var_loo [n_pad], sums [2]}
+ *   9  launch_pred_finalize /       {nt, fitc}; scal {base_var}       {s1|qm, s2|qb [nt]} ->
+ *      launch_fitc_pred_finalize                                       {mu (fitc 0), var [nt]}
+ *   10 launch_surface_point_sums    {n, add_noise}; scal {s2}         {y, alpha, dinv} -> {sums [2]}
+ *   11 launch_dot                   {n}                               {a, b|NULL} -> {out [1]}
+ *   12 launch_pad_copy              {rows, cols, lds, rows_pad,       {src [rows][cols]} ->
+ *                                    cols_pad, ldd, pad_identity}      {dst [rows_pad][ldd]}
+ *   13 launch_local_sum             {n, count}                        {src [n][count]} ->
+ *                                                                      {out [count]}
+ * Entries of mu_loo / var_loo past n are never written and come back NaN. */
+int gps_vec_diag(gps_ctx* ctx, int which, const int64_t* dims, const double* scal,
+                 const double* const* in, double* const* out);
 
 /* on: 0 off, 1 per-kernel-class tags, 2 GEMM tags also carry layout/shape/tri/split-K/lda */
 int gps_prof_enable(gps_ctx* ctx, int on);

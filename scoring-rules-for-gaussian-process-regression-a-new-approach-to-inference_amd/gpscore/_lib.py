@@ -107,6 +107,7 @@ SIGNATURES = {
                                         _P, _P, _P]),
     "gps_fitc_contract_diag": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P, _P, _P, _c_dbl,
                                         _c_int, _PP, _PI64, _P, _PP, _P, _PP, _PP, _P, _P]),
+    "gps_vec_diag": (_c_int, [_c_vp, _c_int, _PI64, _P, _PP, _PP]),
     "gps_prof_enable": (_c_int, [_c_vp, _c_int]),
     "gps_prof_collect": (_c_int, [_c_vp, _c_cp, _c_i64]),
     "gps_phase_enable": (_c_int, [_c_vp, _c_int]),
@@ -303,6 +304,18 @@ def grad_terms_diag_raw(h, which, obj, n, n_pad, ins, outs, scal=1.0, m_pad=0):
     return load().gps_grad_terms_diag(h, which, obj, n, n_pad, m_pad, scal, pi, po)
 
 
+def vec_diag_raw(h, which, dims, scal, ins, outs):
+    """gps_vec_diag: dims up to 8 integers, scal up to 2 doubles, ins / outs lists of float64 arrays
+    or None (None for a list itself: a NULL argument)."""
+    d = np.zeros(8, np.int64)
+    d[:len(dims)] = dims
+    sc = np.zeros(2)
+    sc[:len(scal)] = scal
+    pi = None if ins is None else _ptr_array(ins, 8)
+    po = None if outs is None else _ptr_array(outs, 8)
+    return load().gps_vec_diag(h, which, d.ctypes.data_as(_PI64), ptr(sc), pi, po)
+
+
 def grad_contract_diag_raw(h, n, d, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a, out):
     return load().gps_grad_contract_diag(h, n, d, ptr(X), ptr(inv_ell), sf2, ptr(Ainv), ptr(Mx), ld,
                                          ptr(alpha), ptr(v), ptr(a), ptr(out))
@@ -467,6 +480,11 @@ class Context:
         written in place."""
         self.check(grad_terms_diag_raw(self.h, which, obj, n, n_pad, ins, outs, scal, m_pad),
                    "gps_grad_terms_diag")
+
+    def vec_diag(self, which, dims, ins, outs, scal=()):
+        """One vector-layer launch on host arrays (gps_vec_diag; diagnostics): dims / scal / ins /
+        outs in the header's order, None where an array is absent; outs are written in place."""
+        self.check(vec_diag_raw(self.h, which, dims, scal, ins, outs), "gps_vec_diag")
 
     def grad_contract_diag(self, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a):
         """launch_grad_contract on host arrays (gps_grad_contract_diag; diagnostics): the
