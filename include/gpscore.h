@@ -206,6 +206,17 @@ int gps_dag_task_list_ex(int T, int flags, int kb, int kg, uint32_t* out, int ca
  * in tile form is one word with bit 23 set and part 0, standing for the four strips of its tile.
  * tf = 0 gives gps_dag_task_list_ex's words exactly. */
 int gps_dag_task_list_tf(int T, int flags, int kb, int kg, int tf, uint32_t* out, int cap);
+/* What each of n task words means to the kernel, by the functions the kernel and the generator
+ * use (csrc/dag_task.h): per word GPS_DAG_PROTO_ROW ints in out —
+ *   [0..7]   type, part, fine, i, j, k, len (terms of the K batch), tile (the tile form);
+ *   [8..19]  three polled counts (array, i, j, threshold): the task runs once array[i][j] >=
+ *            threshold for each; array 0 = the A side (acnt), 1 = the X side (xcnt), −1 = unused
+ *            (then i, j, threshold are 0);
+ *   [20..27] two arrivals (array, i, j, increment) added when the task is done, unused as above.
+ * T in 2..64 (the counters' row length); a word of unknown type or with i, j, k (or its batch's
+ * last term) outside the block is refused.  Returns n; needs no device. */
+enum { GPS_DAG_PROTO_ROW = 28 };
+int gps_dag_task_protocol(int T, const uint32_t* words, int n, int32_t* out);
 
 /* Diagnostics: ONE internal FP64 GEMM launch (csrc/kernels_gemm.hip's launch_gemm, through the
  * same gemm() every production caller uses, on the context's main stream with that stream's

@@ -910,6 +910,34 @@ int gps_dag_task_list_tf(int T, int flags, int kb, int kg, int tf, uint32_t* out
   return (int)tl.size();
 }
 
+int gps_dag_task_protocol(int T, const uint32_t* words, int n, int32_t* out) {
+  if (T < 2 || T > 64 || n < 0 || !words || !out) return fail(nullptr, -1, "bad arguments");
+  // a counter as the host handle of the rules: its offset, acnt at 0 and xcnt at T·T
+  auto put = [&](int32_t* q, int off, int v) {
+    q[0] = off < 0 ? -1 : off / (T * T);
+    q[1] = off < 0 ? 0 : off % (T * T) / T;
+    q[2] = off < 0 ? 0 : off % T;
+    q[3] = off < 0 ? 0 : v;
+  };
+  for (int w = 0; w < n; ++w) {
+    const dag::Task t = dag::decode(words[w]);
+    const int last = t.type == 2 ? t.k + t.len - 1 : t.type == 3 ? t.j + t.len - 1 : 0;
+    if (t.type > 4 || t.i >= T || t.j >= T || t.k >= T || last >= T)
+      return fail(nullptr, -1, "task word outside the block");
+    int32_t* row = out + (int64_t)GPS_DAG_PROTO_ROW * w;
+    const int f[8] = {t.type, t.part, t.fine, t.i, t.j, t.k, t.len, t.tile};
+    for (int q = 0; q < 8; ++q) row[q] = f[q];
+    int c[3] = {-1, -1, -1}, v[3] = {0, 0, 0};
+    dag::poll_rule<int>(t.type, t.i, t.j, t.k, t.len, T, 0, T * T, c[0], v[0], c[1], v[1], c[2], v[2]);
+    for (int q = 0; q < 3; ++q) put(row + 8 + 4 * q, c[q], v[q]);
+    int o[2] = {-1, -1}, inc = 0;
+    dag::arrival_rule<int>(t, T, 0, T * T, o[0], inc, o[1]);
+    put(row + 20, o[0], inc);
+    put(row + 24, o[1], 1);
+  }
+  return n;
+}
+
 int gps_phase_enable(gps_ctx* ctx, int on) {
   if (int rc = bind(ctx)) return rc;
   ctx->phase = on != 0;

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "dag_task.h"
+
 #define GPS_TILE 128
 #define GPS_MAX_D 64
 
@@ -454,12 +456,7 @@ struct DagParams {
                                    // check of the batched strips' buffer descriptors only)
 };
 hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s);
-// kb: UPD / UPDX terms of one tile in batches of at most kb (1: every term its own task, the
-// list of before); kg: the last kg terms of every tile stay single tasks; tf: the batches that
-// run in tile form (GPS_OPT_DAG_TILE_FORM's value, 0: none)
-std::vector<uint32_t> dag_task_list(int T, int order = 1, bool fine = true, int kb = 1, int kg = 0,
-                                    int tf = 0);
-inline int64_t dag_cnt_ints(int T) { return (16 + 2 * (int64_t)T * T + 63) / 64 * 64; }
+// (dag_task_list, g_dag_weights, dag_cnt_ints: dag_task.h, included above)
 
 // y[i] = sum_k L[i][k] x[k] over the tile-lower part (rows < n_pad)
 hipError_t launch_gemv_lower(const double* L, int64_t ldl, const double* x, double* y,

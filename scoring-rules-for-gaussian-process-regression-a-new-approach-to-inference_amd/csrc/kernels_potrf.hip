@@ -4,8 +4,6 @@
 // (The round-1 register-blocked VALU kernel, 51 µs, is kept outside the library as the A/B
 // baseline: tools/leaf_v3.hip, tools/diag_bench.cpp.)
 #include <algorithm>
-#include <queue>
-#include <vector>
 
 #include "gps_internal.h"
 
@@ -481,8 +479,8 @@ __global__ __launch_bounds__(256) void potrf_leaf_v4_kernel(
 // triangular operand's nonzeros.  Arrival counters per tile: A-side acnt[i][j] (+4 per UPD, +4
 // per TRSM, +1 per LEAF) and X-side xcnt[i][k] (+4 per UPDX / FIN, +1 per LEAF); a task polls
 // the counts it needs (one lane, relaxed agent-scope loads, bounded) — every input of a task
-// was written by tasks earlier in the queue, so the queue order (a topological order, host
-// side: dag_task_list) guarantees progress for any residency.  Hand-offs follow the
+// was written by tasks earlier in the queue, so the queue order (a topological order:
+// dag_task_list, dag_schedule.hip) guarantees progress for any residency.  Hand-offs follow the
 // write-through form of cdna_hip_programming.md §6 Guideline 16: payload stores `sc1`, every
 // wave drains (vmcnt 0), barrier, one relaxed agent atomic add; consumers load `sc1`.
 namespace dag {
@@ -490,10 +488,7 @@ using v4::d4;
 using v4::dv2;
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-constexpr int NP = 4;        // strips per tile task
-constexpr int NPF_TRSM = 8;  // parts of a fine TRSM (16-row strips)
-constexpr int NPF_UPD = 16;  // parts of a fine UPD (16 × 64 blocks)
-constexpr int U = 16;        // arrivals per finished tile task: 4 per strip, 2 / 1 per fine part
+// (NP, NPF_TRSM, NPF_UPD, U, the task word and the counter protocol: dag_task.h)
 constexpr int AUX_SC1 = 16;  // cache-policy bits of the buffer intrinsics: sc1
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const double* base, uint32_t bytes) {
@@ -906,46 +901,15 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
         trow[3] = (unsigned long long)blockIdx.x << 8 | (xcc & 15);
       }
     }
-    const int type = w & 7, part = (w >> 3) & 15, fine = (w >> 7) & 1, ti = (w >> 8) & 63,
-              tj = (w >> 16) & 63, tk = (w >> 24) & 63;
-    // K batch of an UPD / UPDX strip (dag_task_list): terms tk .. tk + len − 1, resp. tj ..
-    const int len = 1 + (int)((w >> 14) & 3) + 4 * (int)((w >> 22) & 1);
-    // ---- the counts this task needs (see the header); up to three, polled by wave 0 (every
-    //      lane loads the same word; the exit test is taken on lane 0's view)
+    const Task task = decode(w);  // (dag_task.h)
+    const int type = task.type, part = task.part, fine = task.fine, ti = task.i, tj = task.j,
+              tk = task.k, len = task.len;
+    // ---- the counts this task needs (poll_rule, dag_task.h); up to three, polled by wave 0
+    //      (every lane loads the same word; the exit test is taken on lane 0's view)
     if (wave == 0) {
       const int* c0 = nullptr; const int* c1 = nullptr; const int* c2 = nullptr;
       int v0 = 0, v1 = 0, v2 = 0;
-      switch (type) {
-        case 0:  // LEAF(k = ti)
-          c0 = acnt + ti * T + ti; v0 = U * ti;
-          break;
-        case 1:  // TRSM(i, k): A_ik final, X_kk from LEAF(k)
-          c0 = acnt + ti * T + tk; v0 = U * tk;
-          c1 = xcnt + tk * T + tk; v1 = 1;
-          break;
-        // (a K batch polls its LAST term's operands: L_ik final means TRSM(i, k) ran, which waited
-        //  for every UPD(i, k, k') — each of which had polled L_ik' final; X_jk likewise through
-        //  FIN(j, k) and the UPDX(j, k, j') — so the last counts imply the others)
-        case 2: {  // UPD(i, j, k .. kl)
-          const int kl = tk + len - 1;
-          c0 = acnt + ti * T + kl; v0 = U * (kl + 1);
-          c1 = acnt + tj * T + kl; v1 = U * (kl + 1);
-          c2 = acnt + ti * T + tj; v2 = U * tk;
-          break;
-        }
-        case 3: {  // UPDX(i, k, j .. jl): L_ij final, X_jk final, S_ik's earlier terms
-          const int jl = tj + len - 1;
-          c0 = acnt + ti * T + jl; v0 = U * (jl + 1);
-          c1 = xcnt + jl * T + tk; v1 = jl == tk ? 1 : U * (jl - tk + 1);
-          c2 = xcnt + ti * T + tk; v2 = U * (tj - tk);
-          break;
-        }
-        case 4:  // FIN(i, k)
-          c0 = xcnt + ti * T + tk; v0 = U * (ti - tk);
-          c1 = xcnt + ti * T + ti; v1 = 1;
-          break;
-        default: break;
-      }
+      poll_rule<const int*>(type, ti, tj, tk, len, T, acnt, xcnt, c0, v0, c1, v1, c2, v2);
       if (!c1) { c1 = c0; v1 = v0; }
       if (!c2) { c2 = c0; v2 = v0; }
       // A lost dependency is declared only after spin_ticks of wall clock with no movement of
@@ -985,6 +949,9 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
       if (tid == 0) trow[1] = __builtin_amdgcn_s_memrealtime();
     }
     const int64_t lda = p.lda, ldl = p.ldl;
+    // The arrivals (out, inc, out2) below are a COPY of arrival_rule (dag_task.h), kept as this
+    // kernel's own text because calling the rule changes its register allocation:
+    // change both together (the CPU tests replay the rule, only the GPU tests run this copy).
     out2 = nullptr;
     srow = !p.sig ? -1 : type == 4 ? ti | (NP * ti) << 8 : (type == 0 && ti == 0) ? 0 : -1;
     if (type == 0) {
@@ -1021,7 +988,7 @@ __global__ __launch_bounds__(256, GPS_DAG_WAVES_PER_EU) void potrf_dag_kernel(Da
         out = acnt + ti * T + tj;
       }
       run_fine(f);
-    } else if (w >> 23 & 1) {  // tile form of a batched UPD / UPDX (off-diagonal tiles only)
+    } else if (task.tile) {  // tile form of a batched UPD / UPDX (off-diagonal tiles only)
       Tile tl;
       const int64_t R = 128 * (int64_t)ti + 64 * (wave >> 1), J = 128 * (int64_t)tj,
                     K = 128 * (int64_t)tk, wc = 64 * (wave & 1);
@@ -1152,165 +1119,6 @@ hipError_t launch_potrf_dag(const DagParams& p, int nwg, hipStream_t s) {
   if (p.group < 2 || p.group > 4) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k, dim3(nwg), dim3(256), 0, s, p);
   return hipGetLastError();
-}
-
-// Queue order of the persistent factorisation's tasks for a block of T tiles: tile tasks with
-// their dependencies, then Kahn's algorithm releasing the ready task of best priority first (so
-// the order is topological whatever the priorities), each tile task expanded into its NP strips.
-//   order 0: earliest estimated start first (a forward critical-path pass; estimated µs: leaf 36,
-//            strip task 4, hand-off 3) — round 3's first build;
-//   order 1: largest upward rank first (the longest estimated path from the task to the end of
-//            the block, with per-type durations), so the updates that feed the next leaves
-//            overtake the bulk of the trailing update (the first leaves waited 20-26 µs behind
-//            it), with the durations the round-4 traces measured (below);
-//   order 2: the same with round 3's weights (leaf 38, strip 9, fine part 4, hand-off 1).
-// fine: the leaf chain's TRSM(k+1,k) and UPD(k+1,k+1,k) as fine parts (8 / 16, see run_fine).
-// (Round 4's split chain — the leaf without its inverse, TRSM(k+1,k) by substitution, an INV task
-// off the chain — measured slower and was removed: profiles/r4_dag_split_ab.txt,
-// profiles/r5_prune_split_chain.diff.)
-// Word: type | part << 3 | fine << 7 | i << 8 | j << 16 | k << 24, i, j, k in 6 bits each; the K
-// batch length − 1 of an UPD / UPDX task (0..7) in bits 14-15 (low) and 22 (high),
-// k resp. j its first term — length field 0 is the single-term task of before.  Bit 23: the tile
-// form of a batch (one word for the whole tile, part 0).
-// order 1's weights, µs: LEAF, fine part, TRSM, UPD, UPDX, FIN strips, hand-off, and the factor
-// of a tile-form task over a strip of its batch (tools/dag_bench overrides them for sweeps; the
-// library never writes them)
-double g_dag_weights[8] = {35.0, 6.0, 9.7, 11.7, 11.2, 9.3, 2.5, 2.0};
-
-std::vector<uint32_t> dag_task_list(int T, int order, bool fine, int kb, int kg, int tf) {
-  // len: the K batch of an UPD / UPDX task (terms k .. k + len − 1, resp. j .. j + len − 1)
-  struct Task { int type, i, j, k, len; std::vector<int> deps; double est = 0.0, rank = 0.0; int tile = 0; };
-  // Tile form (GPS_OPT_DAG_TILE_FORM, tf = minlen | d << 4): a batch of an
-  // off-diagonal tile with at least minlen terms whose last term ends at least d tile columns
-  // short of where the tile is consumed (UPD(i, j, k0..k1−1): j − k1 ≥ d, the tile feeds
-  // TRSM(i, j); UPDX(i, k, j0..j1−1): i − j1 ≥ d, it feeds FIN(i, k)) is ONE queue word, the whole
-  // tile on one workgroup — a function of (T, kb, kg, tf, the tile, the batch) alone.
-  const int tf_min = tf & 15, tf_d = tf >> 4 & 15;
-  auto tile_form = [&](const Task& t) {
-    if (!tf_min || (t.type != 2 && t.type != 3) || t.len < tf_min) return false;
-    return t.type == 2 ? t.i > t.j && t.j - (t.k + t.len) >= tf_d : t.i - (t.j + t.len) >= tf_d;
-  };
-  auto is_fine = [&](const Task& t) {
-    return fine && ((t.type == 1 && t.i == t.k + 1) || (t.type == 2 && t.i == t.k + 1 && t.j == t.i));
-  };
-  // K batches: of the nt terms of a tile, numbered in the order they are applied,
-  // the first nt − keep go in runs of kb from term 0 (the last run shortened) and the last keep
-  // stay single — a function of (kb, kg, the tile) alone, never of the order or the width.
-  // [b0, b1): the run of term t.
-  auto batch_of = [&](int t, int nt, int keep, int& b0, int& b1) {
-    const int nbat = kb > 1 ? std::max(0, nt - keep) : 0;
-    if (t >= nbat) { b0 = t; b1 = t + 1; return; }
-    b0 = t / kb * kb;
-    b1 = std::min(b0 + kb, nbat);
-  };
-  std::vector<Task> tk;
-  std::vector<int> leaf(T), xkk(T), trsm(T * T, -1), fin(T * T, -1);
-  std::vector<int> upd_last(T * T, -1), updx_last(T * T, -1);
-  auto add = [&](int type, int i, int j, int k, int len, std::vector<int> deps) {
-    Task t;
-    t.type = type; t.i = i; t.j = j; t.k = k; t.len = len;
-    t.tile = tile_form(t);
-    for (int d : deps)
-      if (d >= 0) t.deps.push_back(d);
-    tk.push_back(t);
-    return (int)tk.size() - 1;
-  };
-  // factorisation, right-looking (generation order is topological)
-  for (int k = 0; k < T; ++k) {
-    leaf[k] = add(0, k, k, k, 1, {upd_last[k * T + k]});
-    xkk[k] = leaf[k];  // the task X_kk comes from
-    for (int i = k + 1; i < T; ++i) trsm[i * T + k] = add(1, i, k, k, 1, {upd_last[i * T + k], xkk[k]});
-    for (int j = k + 1; j < T; ++j)
-      for (int i = j; i < T; ++i) {
-        // tile (i, j)'s terms k' < j; the chain's UPD(k+1,k+1,k) is a tile's last term and stays
-        // a fine task of its own.  A batch is generated with its last term, when every L it reads
-        // exists.
-        int b0, b1;
-        batch_of(k, j, std::max(kg, fine && i == j ? 1 : 0), b0, b1);
-        if (k != b1 - 1) continue;
-        std::vector<int> deps = {upd_last[i * T + j]};
-        for (int q = b0; q < b1; ++q) { deps.push_back(trsm[i * T + q]); deps.push_back(trsm[j * T + q]); }
-        if (b1 - b0 == 1) deps = {trsm[i * T + k], trsm[j * T + k], upd_last[i * T + j]};
-        upd_last[i * T + j] = add(2, i, j, b0, b1 - b0, deps);
-      }
-  }
-  // inverse: X row j final → its terms pushed into every row i > j
-  auto xfinal = [&](int j, int k) { return j == k ? xkk[k] : fin[j * T + k]; };
-  for (int j = 0; j < T; ++j) {
-    for (int k = 0; k < j; ++k)  // X_jk = −X_jj S_jk once every term j' < j is in
-      fin[j * T + k] = add(4, j, k, k, 1, {updx_last[j * T + k], xkk[j]});
-    for (int i = j + 1; i < T; ++i)
-      for (int k = 0; k <= j; ++k) {
-        int b0, b1;  // tile (i, k)'s terms j' in [k, i), numbered from k
-        batch_of(j - k, i - k, kg, b0, b1);
-        if (j - k != b1 - 1) continue;
-        std::vector<int> deps = {updx_last[i * T + k]};
-        for (int q = b0 + k; q < b1 + k; ++q) { deps.push_back(trsm[i * T + q]); deps.push_back(xfinal(q, k)); }
-        if (b1 - b0 == 1) deps = {trsm[i * T + j], xfinal(j, k), updx_last[i * T + k]};
-        updx_last[i * T + k] = add(3, i, b0 + k, k, b1 - b0, deps);
-      }
-  }
-  const int n = (int)tk.size();
-  std::vector<std::vector<int>> succ(n);
-  std::vector<int> indeg(n, 0);
-  for (int t = 0; t < n; ++t)
-    for (int d : tk[t].deps) { succ[d].push_back(t); ++indeg[t]; }
-  if (order == 0) {
-    auto dur = [&](const Task& t) { return t.type == 0 ? 36.0 : 4.0 * t.len * (t.tile ? 2.0 : 1.0); };
-    for (int t = 0; t < n; ++t)  // generation order is topological
-      for (int d : tk[t].deps) tk[t].est = std::max(tk[t].est, tk[d].est + dur(tk[d]) + 3.0);
-  } else if (order == 2) {  // round 3's weights
-    auto dur = [&](const Task& t) {
-      return t.type == 0 ? 38.0 : is_fine(t) ? 4.0 : 9.0 * t.len * (t.tile ? 2.0 : 1.0);
-    };
-    for (int t = n - 1; t >= 0; --t) {
-      double m = 0.0;
-      for (int s2 : succ[t]) m = std::max(m, tk[s2].rank + 1.0);
-      tk[t].rank = dur(tk[t]) + m;
-      tk[t].est = -tk[t].rank;
-    }
-  } else {
-    // run time per strip task as the round-4 trace measured it (profiles/r4_dag_trace20_*.txt);
-    // the fine parts count 6 (they run 8.5 but 8-16 of them in parallel) and each hand-off 2.5
-    // (profiles/r4_dag_order_ab.txt: 3.6 % off the block against the round-3 weights)
-    const double* w = g_dag_weights;
-    auto dur = [&](const Task& t) {
-      if (is_fine(t)) return w[1];
-      const double tw = t.tile ? w[7] : 1.0;  // (a tile-form task runs its four strips' work)
-      switch (t.type) {
-        case 0: return w[0];
-        case 1: return w[2];
-        case 2: return w[3] * t.len * tw;  // (a K batch weighs as its K)
-        case 3: return w[4] * t.len * tw;
-        default: return w[5];
-      }
-    };
-    for (int t = n - 1; t >= 0; --t) {  // reverse generation order: successors first
-      double m = 0.0;
-      for (int s2 : succ[t]) m = std::max(m, tk[s2].rank + w[6]);
-      tk[t].rank = dur(tk[t]) + m;
-      tk[t].est = -tk[t].rank;  // smallest key first
-    }
-  }
-  std::priority_queue<std::pair<double, int>, std::vector<std::pair<double, int>>,
-                      std::greater<std::pair<double, int>>> ready;
-  for (int t = 0; t < n; ++t)
-    if (!indeg[t]) ready.push({tk[t].est, t});
-  std::vector<uint32_t> out;
-  while (!ready.empty()) {
-    const int t = ready.top().second;
-    ready.pop();
-    const Task& x = tk[t];
-    const bool f = is_fine(x);
-    const int parts = x.type == 0 || x.tile ? 1 : !f ? dag::NP : x.type == 1 ? dag::NPF_TRSM : dag::NPF_UPD;
-    for (int q = 0; q < parts; ++q)
-      out.push_back((uint32_t)x.type | (uint32_t)q << 3 | (uint32_t)f << 7 | (uint32_t)x.i << 8 |
-                    (uint32_t)((x.len - 1) & 3) << 14 | (uint32_t)x.j << 16 |
-                    (uint32_t)((x.len - 1) >> 2) << 22 | (uint32_t)x.tile << 23 | (uint32_t)x.k << 24);
-    for (int s2 : succ[t])
-      if (!--indeg[s2]) ready.push({tk[s2].est, s2});
-  }
-  return out;
 }
 
 hipError_t launch_potrf_leaf(const double* A, int64_t lda, double* Linv, int64_t ldl, double* Lout,

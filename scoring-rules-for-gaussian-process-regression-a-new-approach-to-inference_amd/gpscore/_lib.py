@@ -95,6 +95,7 @@ SIGNATURES = {
     "gps_dag_task_list": (_c_int, [_c_int, _c_int, _c_vp, _c_int]),
     "gps_dag_task_list_ex": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_vp, _c_int]),
     "gps_dag_task_list_tf": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_int]),
+    "gps_dag_task_protocol": (_c_int, [_c_int, _c_vp, _c_int, _PI]),
     "gps_gemm_diag_check": (_c_int, [ctypes.POINTER(GemmDesc), _c_int, _c_int, _c_int, _PI, _c_int,
                                      _c_int]),
     "gps_gemm_schedule": (_c_i64, [ctypes.POINTER(GemmDesc), _PI, _c_int, _c_int, _PI, _PI, _c_i64]),
@@ -202,6 +203,22 @@ def gemm_schedule(desc, kr=None, have_kscale=False, slots=512):
     lib.gps_gemm_schedule(ctypes.byref(desc), krp, int(have_kscale), slots, pp,
                           items.ctypes.data_as(_PI), n)
     return dict(zip(GEMM_PLAN_NAMES, (int(v) for v in plan))), items
+
+
+DAG_PROTO_ROW = 28  # GPS_DAG_PROTO_ROW
+
+
+def dag_task_protocol(T, words):
+    """[n][DAG_PROTO_ROW] int32 of the persistent factorisation's task words (gps_dag_task_protocol;
+    no device): per word its fields type, part, fine, i, j, k, len, tile, three polled
+    (array, i, j, threshold) and two arrival (array, i, j, increment) groups, array −1 = unused."""
+    lib = load()
+    words = np.ascontiguousarray(words, np.uint32)
+    out = np.zeros((len(words), DAG_PROTO_ROW), np.int32)
+    if len(words) and lib.gps_dag_task_protocol(T, words.ctypes.data, len(words),
+                                                out.ctypes.data_as(_PI)) != len(words):
+        raise GpsError(lib.gps_last_error(None).decode())
+    return out
 
 
 class GpsError(RuntimeError):

@@ -18,90 +18,31 @@ import ctypes
 import numpy as np
 import pytest
 
+import dag_model as M
 import factor_cases as fc
-from test_dag_logic import NP_, NPF, U, task_list
+from dag_model import NP_, NPF, U, arrival, final_counts, inputs, polled, replay
+from test_dag_logic import task_list
 
 E = fc.TILE  # the emulated tile edge: the device's
 TS = (2, 3, 4, 5, 8, 9, 20, 21, 40, 64)
 BS = (1, 2, 4, 8)
 GS = (0, 1, 2)
-ORDER_FLAG = {0: 3, 1: 1, 2: 2}
 
 
 def raw_list(T, kb, kg, order=1, fine=1):
+    """The words of gps_dag_task_list_ex itself."""
     from gpscore import _lib
     lib = _lib.load()
-    flags = fine | (ORDER_FLAG[order] << 2)
-    n = lib.gps_dag_task_list_ex(T, flags, kb, kg, None, 0)
+    n = lib.gps_dag_task_list_ex(T, M.flags(order, fine), kb, kg, None, 0)
     assert n > 0
     out = (ctypes.c_uint32 * n)()
-    assert lib.gps_dag_task_list_ex(T, flags, kb, kg, ctypes.cast(out, ctypes.c_void_p), n) == n
+    assert lib.gps_dag_task_list_ex(T, M.flags(order, fine), kb, kg, ctypes.cast(out, ctypes.c_void_p), n) == n
     return np.frombuffer(out, dtype=np.uint32).copy()
 
 
 def decode(words):
     """(type, part, i, j, k, fine, len) per word; k (UPD) resp. j (UPDX) the batch's first term."""
-    w = words.astype(np.int64)
-    cols = (w & 7, (w >> 3) & 15, (w >> 8) & 63, (w >> 16) & 63, (w >> 24) & 63, (w >> 7) & 1,
-            1 + ((w >> 14) & 3) + 4 * ((w >> 22) & 1))
-    return list(zip(*(c.tolist() for c in cols)))
-
-
-def polled(t):
-    """(counter array, i, j, threshold) the kernel polls for a strip (its switch)."""
-    typ, _, i, j, k, _, ln = t
-    if typ == 0:
-        return [("a", i, i, U * i)]
-    if typ == 1:
-        return [("a", i, k, U * k), ("x", k, k, 1)]
-    if typ == 2:
-        kl = k + ln - 1
-        return [("a", i, kl, U * (kl + 1)), ("a", j, kl, U * (kl + 1)), ("a", i, j, U * k)]
-    if typ == 3:
-        jl = j + ln - 1
-        return [("a", i, jl, U * (jl + 1)), ("x", jl, k, 1 if jl == k else U * (jl - k + 1)),
-                ("x", i, k, U * (j - k))]
-    return [("x", i, k, U * (i - k)), ("x", i, i, 1)]
-
-
-def inputs(t):
-    """The counts that say every tile the strip READS is final (and its own tile's earlier terms
-    are in): the legacy thresholds of every term of the batch."""
-    typ, _, i, j, k, _, ln = t
-    if typ == 2:
-        need = [("a", i, j, U * k)]
-        for q in range(k, k + ln):
-            need += [("a", i, q, U * (q + 1)), ("a", j, q, U * (q + 1))]
-        return need
-    if typ == 3:
-        need = [("x", i, k, U * (j - k))]
-        for q in range(j, j + ln):
-            need += [("a", i, q, U * (q + 1)), ("x", q, k, 1 if q == k else U * (q - k + 1))]
-        return need
-    return polled(t)
-
-
-def arrival(t):
-    """(counter array, i, j, increment)s a finished strip adds."""
-    typ, _, i, j, k, fine, ln = t
-    if typ == 0:
-        return [("a", i, i, 1), ("x", i, i, 1)]
-    if fine:
-        return [("a", i, k if typ == 1 else j, U // NPF[typ])]
-    if typ == 1:
-        return [("a", i, k, U // NP_)]
-    if typ == 2:
-        return [("a", i, j, ln * (U // NP_))]
-    return [("x", i, k, (ln if typ == 3 else 1) * (U // NP_))]
-
-
-def final_counts(T):
-    a, x = np.zeros((T, T), int), np.zeros((T, T), int)
-    for i in range(T):
-        a[i, i], x[i, i] = U * i + 1, 1
-        for j in range(i):
-            a[i, j], x[i, j] = U * (j + 1), U * (i - j + 1)
-    return a, x
+    return [t[:7] for t in M.decode(words)]
 
 
 @pytest.mark.parametrize("T", TS)
@@ -114,9 +55,9 @@ def test_lists(T):
     for order in (0, 1, 2):
         legacy = task_list(T, 1, order)
         for fine in (0, 1):
-            n = lib.gps_dag_task_list(T, fine | (ORDER_FLAG[order] << 2), None, 0)
+            n = lib.gps_dag_task_list(T, M.flags(order, fine), None, 0)
             old = (ctypes.c_uint32 * n)()
-            lib.gps_dag_task_list(T, fine | (ORDER_FLAG[order] << 2), ctypes.cast(old, ctypes.c_void_p), n)
+            lib.gps_dag_task_list(T, M.flags(order, fine), ctypes.cast(old, ctypes.c_void_p), n)
             for g in GS:  # batching off: word for word, whatever g
                 assert np.array_equal(raw_list(T, 1, g, order, fine), np.frombuffer(old, dtype=np.uint32))
         assert [t[:6] for t in decode(raw_list(T, 1, 0, order))] == legacy
@@ -184,86 +125,6 @@ def test_ex_rejections_and_sizes():
 
 
 # ------------------------------------------------------------------ numpy replay, 128-tiles
-class Emu:
-    """A (lower tiles, in place), X = L⁻¹ (stale NaNs until written), the leaves' L_kk."""
-
-    def __init__(self, A, T):
-        self.T, self.A = T, A.copy()
-        self.X = np.full_like(A, np.nan)
-        self.Ld = {}
-        self.cnt = {"a": np.zeros((T, T), int), "x": np.zeros((T, T), int)}
-
-    def met(self, needs):
-        return all(self.cnt[a][i, j] >= v for a, i, j, v in needs)
-
-    @staticmethod
-    def blk(M, i, j, ni=1, nj=1):
-        return M[i * E:(i + ni) * E, j * E:(j + nj) * E]
-
-    def run(self, t):
-        typ, part, i, j, k, fine, ln = t
-        A, X, blk = self.A, self.X, self.blk
-        s = E // NP_
-        rows = slice(part * s, (part + 1) * s)
-        if typ == 0:
-            D = blk(A, i, i)
-            L = np.linalg.cholesky(np.tril(D) + np.tril(D, -1).T)
-            self.Ld[i] = L
-            blk(X, i, i)[:] = np.tril(np.linalg.inv(L))
-        elif fine and typ == 1:
-            e = E // 8
-            C = blk(A, i, k)
-            C[part * e:(part + 1) * e] = C[part * e:(part + 1) * e] @ blk(X, k, k).T
-        elif fine:
-            e = E // 8
-            rb, h = part >> 1, part & 1
-            rws, cols = slice(rb * e, (rb + 1) * e), slice(h * E // 2, (h + 1) * E // 2)
-            upd = blk(A, i, k)[rws] @ blk(A, j, k)[cols].T
-            upd[:, (np.arange(h * E // 2, (h + 1) * E // 2) // e) > rb] = 0.0
-            blk(A, i, j)[rws, cols] -= upd
-        elif typ == 1:
-            C = blk(A, i, k)
-            C[rows] = C[rows] @ blk(X, k, k).T
-        elif typ == 2:  # one product over the batch's K tiles
-            upd = blk(A, i, k, 1, ln)[rows] @ blk(A, j, k, 1, ln).T
-            if i == j:
-                upd[:, (part + 1) * s:] = 0.0
-            blk(A, i, j)[rows] -= upd
-        elif typ == 3:
-            prod = blk(A, i, j, 1, ln)[rows] @ blk(X, j, k, ln, 1)
-            C = blk(X, i, k)
-            C[rows] = prod if j == k else C[rows] + prod
-        else:
-            C = blk(X, i, k)
-            C[:, rows] = -blk(X, i, i) @ C[:, rows]
-        for a, p, q, v in arrival(t):
-            self.cnt[a][p, q] += v
-
-    def factors(self):
-        L = np.tril(self.A, -1)
-        for i, Lkk in self.Ld.items():
-            self.blk(L, i, i)[:] = Lkk
-        return L, np.tril(self.X)
-
-
-def replay(tl, T, A, workers, latest):
-    """`workers` emulated workgroups fetch the queue in order, each holding one task until its
-    polled counts are met; among the ready ones the earliest (or the latest) fetched runs next."""
-    em = Emu(A, T)
-    head, held = 0, []
-    while head < len(tl) or held:
-        while len(held) < workers and head < len(tl):
-            held.append((head, tl[head]))
-            head += 1
-        ready = [x for x in held if em.met(polled(x[1]))]
-        assert ready, "no held task can run: the queue order does not guarantee progress"
-        pick = max(ready) if latest else min(ready)
-        assert em.met(inputs(pick[1])), pick   # the polled counts imply every input final
-        em.run(pick[1])
-        held.remove(pick)
-    return em.factors()
-
-
 @pytest.mark.parametrize("g", GS)
 @pytest.mark.parametrize("kb", (2, 4, 8))
 @pytest.mark.parametrize("T", (3, 5, 8))

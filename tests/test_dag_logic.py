@@ -9,112 +9,29 @@ counters (kernels_potrf.hip, dag::potrf_dag_kernel).
   thresholds encode every true data dependency.
 Reference: torch.potrf KF:26 / KF:332, chol_solve(I, A) KF:242 — numpy.linalg here.
 """
+import functools
+
 import numpy as np
 import pytest
 
-NP_ = 4  # strips per tile task (dag::NP)
-NPF = {1: 8, 2: 16}  # fine parts of the chain's TRSM / UPD (dag::NPF_TRSM, NPF_UPD)
-U = 16   # arrivals per finished tile task (dag::U)
+import dag_model as M
+from dag_model import NP_, NPF
+
 B = 8    # emulated tile edge (the device uses 128; the algebra is edge-independent)
+Emu = functools.partial(M.Emu, edge=B)
 
 
 def task_list(T, fine=1, order=1):
-    """Queue words decoded as (type, part, i, j, k, fine); order as GPS_OPT_DAG_ORDER."""
+    """Queue words of the legacy call gps_dag_task_list itself, decoded as
+    (type, part, i, j, k, fine); order as GPS_OPT_DAG_ORDER."""
     import ctypes
     from gpscore import _lib
     lib = _lib.load()
-    flags = fine | ({0: 3, 1: 1, 2: 2}[order] << 2)
-    n = lib.gps_dag_task_list(T, flags, None, 0)
+    n = lib.gps_dag_task_list(T, M.flags(order, fine), None, 0)
     assert n > 0
     out = (ctypes.c_uint32 * n)()
-    assert lib.gps_dag_task_list(T, flags, ctypes.cast(out, ctypes.c_void_p), n) == n
-    return [(w & 7, (w >> 3) & 15, (w >> 8) & 255, (w >> 16) & 255, (w >> 24) & 255, (w >> 7) & 1)
-            for w in out]
-
-
-def needs(t, T):
-    """(counter array, i, j, threshold) pairs a strip task polls (the kernel's switch)."""
-    typ, _, i, j, k, _ = t
-    if typ == 0:
-        return [("a", i, i, U * i)]
-    if typ == 1:
-        return [("a", i, k, U * k), ("x", k, k, 1)]
-    if typ == 2:
-        return [("a", i, k, U * (k + 1)), ("a", j, k, U * (k + 1)), ("a", i, j, U * k)]
-    if typ == 3:
-        return [("a", i, j, U * (j + 1)), ("x", j, k, 1 if j == k else U * (j - k + 1)),
-                ("x", i, k, U * (j - k))]
-    return [("x", i, k, U * (i - k)), ("x", i, i, 1)]
-
-
-class Emu:
-    """A (lower tiles, in place: L_ik lands in A_ik) and X (L⁻¹) of T×T tiles of edge B."""
-
-    def __init__(self, A, T):
-        self.T = T
-        self.A = A.copy()
-        self.X = np.full_like(A, np.nan)  # stale contents: every tile must be written first
-        self.cnt = {"a": np.zeros((T, T), int), "x": np.zeros((T, T), int)}
-
-    def ready(self, t):
-        return all(self.cnt[a][i, j] >= v for a, i, j, v in needs(t, self.T))
-
-    def blk(self, M, i, j):
-        return M[i * B:(i + 1) * B, j * B:(j + 1) * B]
-
-    def run(self, t):
-        typ, part, i, j, k, fine = t
-        if fine:
-            return self.run_fine(typ, part, i, j, k)
-        s = B // NP_  # strip width (32 of 128 on the device)
-        rows = slice(part * s, (part + 1) * s)
-        if typ == 0:  # LEAF(k = i): the leaf reads A_kk's lower triangle
-            L = np.linalg.cholesky(np.tril(self.blk(self.A, i, i)) + np.tril(self.blk(self.A, i, i), -1).T)
-            self.blk(self.X, i, i)[:] = np.linalg.inv(L)
-            self.cnt["a"][i, i] += 1
-            self.cnt["x"][i, i] += 1
-            return
-        if typ == 1:  # TRSM(i, k): row strip of L_ik = A_ik X_kkᵀ (in place)
-            C = self.blk(self.A, i, k)
-            C[rows] = C[rows] @ self.blk(self.X, k, k).T
-            self.cnt["a"][i, k] += U // NP_
-        elif typ == 2:  # UPD(i, j, k): row strip of A_ij −= L_ik L_jkᵀ (diagonal: lower blocks)
-            C = self.blk(self.A, i, j)
-            upd = self.blk(self.A, i, k)[rows] @ self.blk(self.A, j, k).T
-            if i == j:  # waves right of the strip's diagonal block stay idle
-                upd[:, (part + 1) * s:] = 0.0
-            C[rows] -= upd
-            self.cnt["a"][i, j] += U // NP_
-        elif typ == 3:  # UPDX(i, k, j): row strip of S_ik (+)= L_ij X_jk (first term overwrites)
-            C = self.blk(self.X, i, k)
-            prod = self.blk(self.A, i, j)[rows] @ self.blk(self.X, j, k)
-            C[rows] = prod if j == k else C[rows] + prod
-            self.cnt["x"][i, k] += U // NP_
-        else:  # FIN(i, k): column strip of X_ik = −X_ii S_ik (in place)
-            C = self.blk(self.X, i, k)
-            C[:, rows] = -self.blk(self.X, i, i) @ C[:, rows]
-            self.cnt["x"][i, k] += U // NP_
-
-    def run_fine(self, typ, part, i, j, k):
-        """The chain's fine parts: TRSM(k+1,k) by 16-row strips (B/8 here), UPD(k+1,k+1,k) by
-        (row block, column half) with the blocks right of the diagonal block idle."""
-        e = B // 8  # the device's 16-row block
-        if typ == 1:
-            assert i == k + 1
-            C = self.blk(self.A, i, k)
-            rows = slice(part * e, (part + 1) * e)
-            C[rows] = C[rows] @ self.blk(self.X, k, k).T
-            self.cnt["a"][i, k] += U // NPF[1]
-            return
-        assert typ == 2 and i == j == k + 1
-        rb, h = part >> 1, part & 1
-        rows, cols = slice(rb * e, (rb + 1) * e), slice(h * B // 2, (h + 1) * B // 2)
-        upd = self.blk(self.A, i, k)[rows] @ self.blk(self.A, j, k)[cols].T
-        for c in range(upd.shape[1]):  # column block of the wave
-            if (h * B // 2 + c) // e > rb:
-                upd[:, c] = 0.0
-        self.blk(self.A, i, j)[rows, cols] -= upd
-        self.cnt["a"][i, j] += U // NPF[2]
+    assert lib.gps_dag_task_list(T, M.flags(order, fine), ctypes.cast(out, ctypes.c_void_p), n) == n
+    return [t[:6] for t in M.decode(np.frombuffer(out, dtype=np.uint32))]
 
 
 def spd(T, seed):

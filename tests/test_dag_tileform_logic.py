@@ -18,38 +18,23 @@ Checked here:
   emulated tile-form task runs its four strips' products: per output element the device's chain
   is the strip's, which is what the GPU tests assert bitwise.)
 """
-import ctypes
-
 import numpy as np
 import pytest
 
+import dag_model as M
 import factor_cases as fc
-from test_dag_kbatch_logic import (E, ORDER_FLAG, Emu, arrival, decode, final_counts, inputs, polled,
-                                   raw_list)
-from test_dag_logic import NP_, NPF, U
+from dag_model import NP_, NPF, arrival, final_counts, inputs, polled, replay, tf_of
+from test_dag_kbatch_logic import E, decode, raw_list
 
 BS = (2, 4, 8)
 FORMS = ((0, 2), (1, 2), (3, 4), (1, 8))   # (d, minlen)
 
 
-def tf_of(d, minlen):
-    return minlen | d << 4
-
-
 def raw_list_tf(T, kb, kg, tf, order=1, fine=1):
-    from gpscore import _lib
-    lib = _lib.load()
-    flags = fine | (ORDER_FLAG[order] << 2)
-    n = lib.gps_dag_task_list_tf(T, flags, kb, kg, tf, None, 0)
-    assert n > 0
-    out = (ctypes.c_uint32 * n)()
-    assert lib.gps_dag_task_list_tf(T, flags, kb, kg, tf, ctypes.cast(out, ctypes.c_void_p), n) == n
-    return np.frombuffer(out, dtype=np.uint32).copy()
+    return M.task_list(T, order, fine, kb, kg, tf)
 
 
-def decode_tf(words):
-    """decode()'s tuples with the tile-form bit appended."""
-    return [t + (int(w) >> 23 & 1,) for t, w in zip(decode(words), words.tolist())]
+decode_tf = M.decode   # decode()'s tuples with the tile-form bit appended
 
 
 def rule(t, d, minlen):
@@ -58,11 +43,6 @@ def rule(t, d, minlen):
     if fine or typ not in (2, 3) or ln < minlen:
         return False
     return (i > j and j - (k + ln) >= d) if typ == 2 else i - (j + ln) >= d
-
-
-def tile_arrival(t):
-    typ, _, i, j, k, _, ln = t
-    return [("a", i, j, ln * U)] if typ == 2 else [("x", i, k, ln * U)]
 
 
 def test_form_off_is_the_strip_list():
@@ -110,14 +90,14 @@ def test_lists(T):
                     typ, part, i, j, k, fine, ln = t
                     if tile:
                         assert part == 0 and not fine and typ in (2, 3) and i > (j if typ == 2 else k), t
-                        parts, arr = 1, tile_arrival(t)
+                        parts, arr = 1, arrival(tl[at])
                     else:
                         parts = 1 if typ == 0 else NPF[typ] if fine else NP_
                         assert [x[:7] for x in tl[at:at + parts]] == [(typ, q, i, j, k, fine, ln) for q in range(parts)], t
                         assert not any(x[7] for x in tl[at:at + parts])
                         arr = [(a, p, q, v * parts) for a, p, q, v in arrival(t)]
                     at += parts
-                    assert all(cnt[a][p][q] >= v for a, p, q, v in polled(t)), t   # topological
+                    assert all(cnt[a][p][q] >= v for a, p, q, v in polled(t + (tile,))), t   # topological
                     assert all(cnt[a][p][q] >= v for a, p, q, v in inputs(t)), t   # polled => every input
                     for a, p, q, v in arr:
                         cnt[a][p][q] += v
@@ -146,33 +126,6 @@ def test_the_gpu_cases_have_what_they_say():
 
 
 # ------------------------------------------------------------------ numpy replay, 128-tiles
-def run(em, t):
-    if not t[7]:
-        return em.run(t[:7])
-    typ, _, i, j, k, fine, ln = t[:7]
-    for part in range(NP_):   # the four strips' products; one arrival of len · U
-        em.run((typ, part, i, j, k, fine, ln))
-
-
-def replay(tl, T, A, workers, latest):
-    """test_dag_kbatch_logic.replay with tile-form words."""
-    em = Emu(A, T)
-    head, held = 0, []
-    while head < len(tl) or held:
-        while len(held) < workers and head < len(tl):
-            held.append((head, tl[head]))
-            head += 1
-        ready = [x for x in held if em.met(polled(x[1][:7]))]
-        assert ready, "no held task can run: the queue order does not guarantee progress"
-        pick = max(ready) if latest else min(ready)
-        assert em.met(inputs(pick[1][:7])), pick
-        run(em, pick[1])
-        held.remove(pick)
-    fa, fx = final_counts(T)
-    assert np.array_equal(em.cnt["a"], fa) and np.array_equal(em.cnt["x"], fx)
-    return em.factors()
-
-
 @pytest.mark.parametrize("d,minlen", ((0, 2), (1, 2), (0, 1)))
 @pytest.mark.parametrize("kb", BS)
 @pytest.mark.parametrize("T", (5, 8))

@@ -15,7 +15,7 @@ import pytest
 import factor_cases as FC
 import gp_oracle as O
 from conftest import nrel
-from test_dag_kbatch_logic import decode, raw_list
+from dag_model import decode, task_list
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +42,7 @@ def tiles(T, kb, kg):
     """Per (type, tile row, tile column): the sorted (first term within the tile, length) of its
     UPD / UPDX tasks in the queue."""
     out = {}
-    for typ, part, i, j, k, fine, ln in decode(raw_list(T, kb, kg)):
+    for typ, part, i, j, k, fine, ln, _ in decode(task_list(T, kb=kb, kg=kg)):
         if typ in (2, 3) and part == 0:
             key, first = ((typ, i, j), k) if typ == 2 else ((typ, i, k), j - k)
             out.setdefault(key, []).append((first, ln))

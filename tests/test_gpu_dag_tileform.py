@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import factor_cases as FC
-from test_dag_tileform_logic import decode_tf, raw_list_tf, tf_of
+from dag_model import decode, task_list, tf_of
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,7 @@ def same(a, b):
 
 
 def tile_words(T, kb, tf):
-    return [t for t in decode_tf(raw_list_tf(T, kb, 0, tf)) if t[7]]
+    return [t for t in decode(task_list(T, kb=kb, tf=tf)) if t[7]]
 
 
 CASES = [(5, 2, tf_of(0, 2), "a"), (5, 2, tf_of(0, 2), "b6"), (11, 8, tf_of(1, 2), "a"),
@@ -57,7 +57,7 @@ def test_case_lists():
     tw = tile_words(5, 2, tf_of(0, 2))
     assert any(t[0] == 2 for t in tw) and any(t[0] == 3 and t[3] > t[4] for t in tw)
     assert any(t[0] == 3 and t[3] == t[4] for t in tw)   # a batch holding the clipped first term
-    tl = decode_tf(raw_list_tf(11, 8, 0, tf_of(1, 2)))
+    tl = decode(task_list(11, kb=8, tf=tf_of(1, 2)))
     assert (2, 0, 10, 9, 0, 0, 8, 1) in tl and (2, 0, 10, 9, 8, 0, 1, 0) in tl
 
 

@@ -141,11 +141,10 @@ int main(int argc, char** argv) {
     double bflop = 0.0, bticks = 0.0, rticks = 0.0, tflop = 0.0, tticks = 0.0, trticks = 0.0;
     long nb = 0, ntf = 0;
     for (int t = 0; t < nt; ++t) {
-      const uint32_t w = tl[t];
-      const int type = w & 7, part = (w >> 3) & 15, fn = (w >> 7) & 1, i = (w >> 8) & 63, j = (w >> 16) & 63,
-                k = (w >> 24) & 63, len = 1 + ((w >> 14) & 3) + 4 * ((w >> 22) & 1);
-      if (fn || (type != 2 && type != 3)) continue;
-      if (w >> 23 & 1) {  // tile form: four 64×64 blocks, the clipped first UPDX term from 64·(w & 1)
+      const dag::Task w = dag::decode(tl[t]);
+      const int type = w.type, part = w.part, i = w.i, j = w.j, k = w.k, len = w.len;
+      if (w.fine || (type != 2 && type != 3)) continue;
+      if (w.tile) {  // tile form: four 64×64 blocks, the clipped first UPDX term from 64·(w & 1)
         tflop += 4.0 * 2.0 * 64 * 64 * 128.0 * len - (type == 3 && j == k ? 2.0 * 2.0 * 64 * 64 * 64.0 : 0.0);
         tticks += (double)(tr[4 * t + 2] - tr[4 * t]);
         trticks += (double)(tr[4 * t + 2] - tr[4 * t + 1]);

@@ -4,6 +4,7 @@ the leaf chain step by step (LEAF(k) -> TRSM(k+1,k) -> UPD(k+1,k+1,k) -> LEAF(k+
 hand-off latency (a consumer's ready time minus the done time of the last producer it waited on).
 Usage: python tools/dag_trace.py trace.csv"""
 import csv
+import os
 import sys
 from collections import defaultdict
 
@@ -12,14 +13,17 @@ TICK_US = 0.01  # s_memrealtime runs at 100 MHz
 
 
 def load(path):
+    """The CSV's rows, each word decoded by the library (gps_dag_task_protocol, csrc/dag_task.h)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                    "scoring-rules-for-gaussian-process-regression-a-new-approach-to-inference_amd"))
+    from gpscore import _lib
+    recs = list(csv.DictReader(open(path)))
+    proto = _lib.dag_task_protocol(64, [int(r["word"]) for r in recs]).tolist()
     rows = []
-    for r in csv.DictReader(open(path)):
-        w = int(r["word"])
-        rows.append(dict(slot=int(r["slot"]), type=w & 7, part=(w >> 3) & 15, fine=(w >> 7) & 1, i=(w >> 8) & 63,
-                         j=(w >> 16) & 63, k=(w >> 24) & 63,  # (bits 14-15, 22: a K batch's length − 1)
-                         len=1 + ((w >> 14) & 3) + 4 * ((w >> 22) & 1), fetch=int(r["fetch"]),
-                         ready=int(r["ready"]), done=int(r["done"]), wg=int(r["wg"]),
-                         xcc=int(r["xcc"])))
+    for r, (typ, part, fine, i, j, k, ln, tile, *_) in zip(recs, proto):
+        rows.append(dict(slot=int(r["slot"]), type=typ, part=part, fine=fine, i=i, j=j, k=k, len=ln,
+                         fetch=int(r["fetch"]), ready=int(r["ready"]), done=int(r["done"]),
+                         wg=int(r["wg"]), xcc=int(r["xcc"])))
     t0 = min(r["fetch"] for r in rows)
     for r in rows:
         for key in ("fetch", "ready", "done"):
