@@ -714,6 +714,38 @@ int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfol
                                  double* theta_out, double* values, double* thetas, double* obj,
                                  double* mu, double* var, double* sc, int* info, int* steps_done);
 
+/* ---- batches of full GPs of up to 512 rows on the block-LOO energy score --------
+ * gps_full_blockloo_es (KF:607-663) and the SGD fit around it (KF:665-732: 25 steps at lr 0.1,
+ * 300 draws a fold, redrawn every step) for a whole batch: the model, limits (1 <= n <= 512, d <=
+ * 16, n_ell = 1 or d, GPS_ARD or GPS_RBF, 2 <= nfold <= min(n, 32)), SGD loop, final pass,
+ * outputs (which may be NULL included), GPS_BATCH_STALE_NOISE and failure semantics of
+ * gps_full_blockloo_*_tall, and further ceil(n / nfold) <= 128 (a fold is at most two tiles on a
+ * side: its O(b³) square-root work has to fit one launch), 2 <= num_sim <= 512, 0 < beta <= 2.
+ * draws holds nprob × draw_sets × 2·num_sim·n doubles, every set in gps_full_blockloo_es's layout
+ * (per fold [a, a + b): ξ then ξ', num_sim × b each, at 2·num_sim·a); the value + gradient call
+ * reads one set a problem, training step i reads set i mod draw_sets, 1 <= draw_sets <= max(itr,
+ * 1): draw_sets = itr is the scripts' fresh draws every step, draw_sets = 1 common random numbers.
+ * A step is three launches — per problem, per (problem, fold), per problem — and one step runs per
+ * launch sequence; results are bitwise independent of nprob, the problem's position and how itr
+ * is split over calls chained through θ.  info[q] is 0, k in 1..n, n + k (as
+ * gps_full_blockloo_*_tall) or 2n + 1 + f: fold f's Newton–Schulz schedule would need more than
+ * 40 steps (σ² below ~1e-24 of ‖Π_f‖∞).  The per-problem workspace is 3·np² + 2·np + 72 +
+ * nfold·(11·bp² + 6·Sp·bp + Sp²) doubles (np, bp as above, Sp = 64·ceil((num_sim + 1)/64)); a
+ * batch whose inputs (the draws included), outputs or workspace exceed 8 GiB is refused: fewer
+ * draw_sets or a smaller batch are the ways out.  They agree with gps_full_blockloo_es within
+ * rounding, never bitwise. */
+int gps_full_es_grad_tall(gps_ctx* ctx, int kind, int nfold, int num_sim, double beta,
+                          int64_t nprob, const double* X, const double* y, int64_t n, int d,
+                          const double* theta, int n_ell, const double* draws, double* value,
+                          double* fold_values, double* obj, double* grad, int* info);
+int gps_full_es_train_tall(gps_ctx* ctx, int kind, int nfold, int num_sim, double beta,
+                           int64_t nprob, const double* X, const double* y, int64_t n, int d,
+                           const double* theta0, int n_ell, int64_t itr, double lr,
+                           const double* Xt, const double* yt, int64_t nt, int flags,
+                           const double* draws, int64_t draw_sets, double* theta_out,
+                           double* values, double* thetas, double* obj, double* mu, double* var,
+                           double* sc, int* info, int* steps_done);
+
 /* ---- batches of tall FITC GPs on the block-LOO objectives ----------------------
  * gps_fitc_grad_tall / gps_fitc_train_tall with the objective GPS_BLOCK_DSS or GPS_BLOCK_KC over
  * nfold folds [int(f·n/nfold), int((f+1)·n/nfold)) (gps_fitc_blockloo's objectives and folds: the

@@ -1,5 +1,5 @@
-// C-ABI, the six "one workgroup per problem" batch paths (DESIGN §19, §20, §22, §24, §25, §26,
-// §27):
+// C-ABI, the seven "one workgroup per problem" batch paths (DESIGN §19, §20, §22, §24, §25, §26,
+// §27, §32):
 //   gps_full_{grad,train}_batch  small full GPs, n <= 128            kernels_batch.hip
 //   gps_fitc_{grad,train}_batch  small FITC GPs, n <= 128, m <= 32   kernels_batch_fitc.hip
 //   gps_fitc_{grad,train}_tall   FITC GPs, n <= 2048                 kernels_batch_fitc_tall.hip
@@ -8,10 +8,13 @@
 //                                                                    kernels_batch_full_tall_block.hip
 //   gps_fitc_blockloo_{grad,train}_tall  the tall FITC GPs on the block-LOO DSS / KC objectives
 //                                                                    kernels_batch_fitc_tall_block.hip
+//   gps_full_es_{grad,train}_tall  the tall full GPs on the block-LOO energy score, the fold work
+//                                  on one workgroup per (problem, fold)
+//                                                                    kernels_batch_full_tall_es.hip
 // value + gradient of every problem at its own θ (and Z), and the SGD fit loops of the scripts'
 // replicate loops for a whole batch with the final predictive and score bundle.  The calls own
 // their device buffers:
-//   btin     X | y | Xt | yt
+//   btin     X | y | Xt | yt | the energy score's draws
 //   btstate  θ (nprob·nth) | stale log σ² (nprob) | Z (nprob·m·d, FITC) | the tall kernels'
 //            per-problem workspace; the full-tall path pads the head to a multiple of 8 doubles
 //            (its workspace is read in 16-byte pieces)
@@ -35,10 +38,15 @@ const char* const kTooBig = "batch: more than 8 GiB of inputs or outputs, split 
 template <class P>
 constexpr bool kFitc = std::is_same<P, BatchFitcParams>::value;
 
-// what only the block-LOO path has: the fold count and BATCH_MODE_GRAD's two extra outputs
+// what only the block-LOO paths have: the fold count and BATCH_MODE_GRAD's two extra outputs; the
+// energy score's draws (device), their sets per problem, num_sim and β
 struct Block {
   int nfold;
   double *value, *fold_values;
+  const double* draws = nullptr;
+  int64_t draw_sets = 0;
+  int num_sim = 0;
+  double beta = 0.0;
 };
 
 template <class P>
@@ -47,49 +55,54 @@ struct Path {
   const char* n_msg;
   const char *grad_tag, *train_tag;
   // workspace doubles per problem behind the state, or NULL
-  int64_t (*ws)(int64_t n, int m, int nfold);
+  int64_t (*ws)(int64_t n, int m, int nfold, int num_sim);
   bool pad;                         // the state's head is padded to a multiple of 8 doubles
   int (*steps)(int64_t n);          // SGD steps one launch may run
-  hipError_t (*launch)(const P& p, double* ws, int64_t ws_stride, const Block& b, hipStream_t s);
+  // (ctx: for a path that times the launches of its sequence one by one)
+  hipError_t (*launch)(gps_ctx* ctx, const P& p, double* ws, int64_t ws_stride, const Block& b,
+                       hipStream_t s);
   bool block;                       // the objective is a GPS_BLOCK_* code over nfold folds
+  bool es = false;                  // that code is GPS_BLOCK_ES: draws, num_sim and β come with it
 };
 
 const Path<BatchParams> kFull = {
     GPS_SURFACE_MAX_N, "batch: n must be in 1..128", "batch_grad", "batch_train", nullptr, false,
     [](int64_t) { return kBatchStepsPerLaunch; },
-    [](const BatchParams& p, double*, int64_t, const Block&, hipStream_t s) {
+    [](gps_ctx*, const BatchParams& p, double*, int64_t, const Block&, hipStream_t s) {
       return launch_batch(p, s);
     },
     false};
 const Path<BatchFitcParams> kFitcSmall = {
     GPS_SURFACE_MAX_N, "batch: n must be in 1..128", "batch_fitc_grad", "batch_fitc_train", nullptr,
     false, [](int64_t) { return kBatchStepsPerLaunch; },
-    [](const BatchFitcParams& p, double*, int64_t, const Block&, hipStream_t s) {
+    [](gps_ctx*, const BatchFitcParams& p, double*, int64_t, const Block&, hipStream_t s) {
       return launch_batch_fitc(p, s);
     },
     false};
 const Path<BatchFitcParams> kFitcTall = {
     GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_grad",
-    "batch_fitc_tall_train", [](int64_t n, int m, int) { return batch_fitc_tall_ws_doubles(n, m); },
+    "batch_fitc_tall_train", [](int64_t n, int m, int, int) { return batch_fitc_tall_ws_doubles(n, m); },
     false, batch_fitc_tall_steps,
-    [](const BatchFitcParams& p, double* ws, int64_t stride, const Block&, hipStream_t s) {
+    [](gps_ctx*, const BatchFitcParams& p, double* ws, int64_t stride, const Block&,
+       hipStream_t s) {
       return launch_batch_fitc_tall(BatchFitcTallParams{p, ws, stride}, s);
     },
     false};
 const Path<BatchParams> kFullTall = {
     GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_grad",
-    "batch_full_tall_train", [](int64_t n, int, int) { return batch_full_tall_ws_doubles(n); },
+    "batch_full_tall_train", [](int64_t n, int, int, int) { return batch_full_tall_ws_doubles(n); },
     true, batch_full_tall_steps,
-    [](const BatchParams& p, double* ws, int64_t stride, const Block&, hipStream_t s) {
+    [](gps_ctx*, const BatchParams& p, double* ws, int64_t stride, const Block&, hipStream_t s) {
       return launch_batch_full_tall(BatchFullTallParams{p, ws, stride}, s);
     },
     false};
 const Path<BatchParams> kFullTallBlock = {
     GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_block_grad",
     "batch_full_tall_block_train",
-    [](int64_t n, int, int nfold) { return batch_full_tall_block_ws_doubles(n, nfold); }, true,
+    [](int64_t n, int, int nfold, int) { return batch_full_tall_block_ws_doubles(n, nfold); }, true,
     batch_full_tall_block_steps,
-    [](const BatchParams& p, double* ws, int64_t stride, const Block& b, hipStream_t s) {
+    [](gps_ctx*, const BatchParams& p, double* ws, int64_t stride, const Block& b,
+       hipStream_t s) {
       return launch_batch_full_tall_block(
           BatchFullTallBlockParams{p, ws, stride, b.nfold, 0, b.value, b.fold_values}, s);
     },
@@ -97,13 +110,39 @@ const Path<BatchParams> kFullTallBlock = {
 const Path<BatchFitcParams> kFitcTallBlock = {
     GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_block_grad",
     "batch_fitc_tall_block_train",
-    [](int64_t n, int m, int nfold) { return batch_fitc_tall_block_ws_doubles(n, m, nfold); },
+    [](int64_t n, int m, int nfold, int) { return batch_fitc_tall_block_ws_doubles(n, m, nfold); },
     false, batch_fitc_tall_block_steps,
-    [](const BatchFitcParams& p, double* ws, int64_t stride, const Block& b, hipStream_t s) {
+    [](gps_ctx*, const BatchFitcParams& p, double* ws, int64_t stride, const Block& b,
+       hipStream_t s) {
       return launch_batch_fitc_tall_block(
           BatchFitcTallBlockParams{p, ws, stride, b.nfold, b.value, b.fold_values}, s);
     },
     true};
+const Path<BatchParams> kFullTallEs = {
+    GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_es_grad",
+    "batch_full_tall_es_train",
+    [](int64_t n, int, int nfold, int num_sim) {
+      return batch_full_tall_es_ws_doubles(n, nfold, num_sim);
+    },
+    true, [](int64_t) { return 1; },  // a step is a launch sequence of its own
+    [](gps_ctx* ctx, const BatchParams& p, double* ws, int64_t stride, const Block& b,
+       hipStream_t s) {
+      const BatchFullTallEsParams tp = {p, ws, stride, b.nfold, b.num_sim, b.beta, b.draws,
+                                        b.draw_sets, b.value, b.fold_values};
+      // the sequence's launches under tags of their own, inside the call's: what the launch-length
+      // rule is held against
+      static const char* const tags[ES_PHASES] = {"batch_full_tall_es_forward",
+                                                  "batch_full_tall_es_folds",
+                                                  "batch_full_tall_es_tail",
+                                                  "batch_full_tall_es_final"};
+      for (int ph = 0; ph < ES_PHASES; ++ph) {
+        Prof pr(ctx, tags[ph], 0, 0);
+        const hipError_t e = launch_batch_full_tall_es(tp, ph, s);
+        if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
+    },
+    true, true};
 
 // what every entry is given; Z and m are NULL and 0, and kind is unused, where the entry has none
 struct Problem {
@@ -117,13 +156,21 @@ struct Problem {
   const double* theta;
   int n_ell;
   int nfold = 0;  // the block-LOO path's fold count
+  // the energy score: num_sim, β, the draws (host) and their sets per problem
+  int num_sim = 0;
+  double beta = 0.0;
+  const double* draws = nullptr;
+  int64_t draw_sets = 0;
+  int64_t n_draws() const { return draws ? nprob * draw_sets * 2 * num_sim * n : 0; }
 };
 
 template <class P>
 int check_problem(gps_ctx* ctx, const Path<P>& path, const Problem& a) {
   ARGCHK(a.X && a.y && (!kFitc<P> || a.Z) && a.theta, "NULL argument");
   if (!kFitc<P>) ARGCHK(a.kind == GPS_ARD || a.kind == GPS_RBF, "kind must be GPS_ARD or GPS_RBF");
-  if (path.block)
+  if (path.es)
+    ARGCHK(a.draws, "NULL argument");
+  else if (path.block)
     ARGCHK(a.objective == GPS_BLOCK_DSS || a.objective == GPS_BLOCK_KC,
            "objective must be GPS_BLOCK_DSS or GPS_BLOCK_KC");
   else
@@ -138,6 +185,14 @@ int check_problem(gps_ctx* ctx, const Path<P>& path, const Problem& a) {
   if (kFitc<P>) ARGCHK(a.m >= 1 && a.m <= GPS_BATCH_FITC_MAX_M, "batch: m must be in 1..32");
   ARGCHK(a.d >= 1 && a.d <= GPS_BATCH_MAX_D, "batch: d must be in 1..16");
   ARGCHK(a.n_ell == 1 || a.n_ell == a.d, "n_ell must be 1 or d");
+  if (path.es) {
+    ARGCHK((a.n + a.nfold - 1) / a.nfold <= GPS_BATCH_ES_MAX_FOLD,
+           "batch: an energy-score fold holds at most 128 rows (ceil(n / nfold) <= 128: a fold's "
+           "O(b^3) square-root work has to fit one launch of ~20 ms), use more folds");
+    ARGCHK(a.num_sim >= 2 && a.num_sim <= GPS_BATCH_ES_MAX_SIM, "batch: num_sim must be in 2..512");
+    ARGCHK(a.beta > 0.0 && a.beta <= 2.0, "beta must be in (0, 2]");
+    ARGCHK(a.draw_sets >= 1, "batch: draw_sets must be at least 1");
+  }
   return 0;
 }
 
@@ -150,7 +205,8 @@ int carve(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t nt, int64
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
   int64_t head = nprob * (nth + 1 + nz);
   if (path.pad) head = (head + 7) / 8 * 8;
-  HIPCHK(ensure(ctx, ctx->btin, (size_t)(nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1)) * 8));
+  HIPCHK(ensure(ctx, ctx->btin,
+                (size_t)(nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + a.n_draws()) * 8));
   HIPCHK(ensure(ctx, ctx->btstate, (size_t)(head + n_ws) * 8));
   HIPCHK(ensure(ctx, ctx->btint, (size_t)(2 * nprob) * sizeof(int)));
   HIPCHK(ensure(ctx, ctx->btout, (size_t)n_out * 8));
@@ -195,6 +251,9 @@ int upload(gps_ctx* ctx, const Problem& a, const P& p, const double* Xt, const d
   else
     HIPCHK(hipMemsetAsync(p.stale, 0, (size_t)nprob * 8, s));
   HIPCHK(hipMemsetAsync(p.info, 0, (size_t)(2 * nprob) * sizeof(int), s));
+  if (a.draws)  // behind the test rows
+    HIPCHK(hipMemcpyAsync((void*)(p.y + nprob * a.n + nprob * p.nt * (a.d + 1)), a.draws,
+                          (size_t)a.n_draws() * 8, hipMemcpyHostToDevice, s));
   return 0;
 }
 
@@ -213,10 +272,12 @@ int grad_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, double* obj, 
   if (int rc = check_problem(ctx, path, a)) return rc;
   ARGCHK(grad && (!kFitc<P> || grad_z) && info && (!path.block || value), "NULL argument");
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
-  const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold) : 0, n_ws = nprob * stride;
+  const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold, a.num_sim) : 0;
+  const int64_t n_ws = nprob * stride;
   const int64_t n_blk = path.block ? nprob * (1 + a.nfold) : 0;
   if (path.ws)  // the small paths' value + gradient calls have no such guard
-    ARGCHK(nprob * a.n * (a.d + 1) + nprob * nz <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
+    ARGCHK(nprob * a.n * (a.d + 1) + nprob * nz + a.n_draws() <= kMaxDoubles &&
+               n_ws <= kMaxDoubles, kTooBig);
   P p;
   double* ws;
   if (int rc = carve(ctx, path, a, 0, nprob * (GPS_N_OBJ + nth + nz) + n_blk, n_ws, p, &ws))
@@ -225,7 +286,7 @@ int grad_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, double* obj, 
   p.obj = ctx->btout.d();
   p.grad = p.obj + nprob * GPS_N_OBJ;
   if constexpr (kFitc<P>) p.grad_z = p.grad + nprob * nth;
-  Block blk = {a.nfold, nullptr, nullptr};
+  Block blk = {a.nfold, nullptr, nullptr, p.y + nprob * a.n, a.draw_sets, a.num_sim, a.beta};
   if (path.block) {
     blk.value = p.grad + nprob * (nth + nz);
     blk.fold_values = blk.value + nprob;
@@ -233,7 +294,7 @@ int grad_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, double* obj, 
   if (int rc = upload(ctx, a, p, nullptr, nullptr, nullptr)) return rc;
   {
     Prof pr(ctx, path.grad_tag, 0, 0);
-    HIPCHK(path.launch(p, ws, stride, blk, ctx->stream));
+    HIPCHK(path.launch(ctx, p, ws, stride, blk, ctx->stream));
   }
   if (path.block) {
     if (int rc = download(ctx, value, blk.value, nprob)) return rc;
@@ -261,13 +322,17 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   if (kFitc<P>) ARGCHK(std::isfinite(lr_z), "batch: lr_z must be finite");
   ARGCHK(nt >= 0 && nt <= (1 << 24), "batch: nt must be in 0..2^24");
   ARGCHK((flags & ~GPS_BATCH_STALE_NOISE) == 0, "unknown batch flag");
+  if (path.es)
+    ARGCHK(a.draw_sets <= std::max<int64_t>(itr, 1), "batch: draw_sets must be at most max(itr, 1)");
   const bool pred = Xt != nullptr && nt > 0;
   if (!pred) nt = 0;
   const bool scored = pred && yt != nullptr;
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
-  const int64_t n_in = nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + nprob * nz;
+  const int64_t n_in =
+      nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + nprob * nz + a.n_draws();
   const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC);
-  const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold) : 0, n_ws = nprob * stride;
+  const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold, a.num_sim) : 0;
+  const int64_t n_ws = nprob * stride;
   ARGCHK(n_in <= kMaxDoubles && n_out <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
   P p;
   double* ws;
@@ -301,7 +366,10 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
       p.step0 = (int)step;
       p.nsteps = (int)ns;
       p.do_final = step + ns == itr;
-      HIPCHK(path.launch(p, ws, stride, Block{a.nfold, nullptr, nullptr}, ctx->stream));
+      HIPCHK(path.launch(ctx, p, ws, stride,
+                         Block{a.nfold, nullptr, nullptr, p.y + nprob * a.n + nprob * nt * (a.d + 1),
+                               a.draw_sets, a.num_sim, a.beta},
+                         ctx->stream));
       step += ns;
     } while (step < itr);
   }
@@ -377,6 +445,30 @@ int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfol
                     {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell, nfold}, itr, lr,
                     0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu, var, sc,
                     info, steps_done);
+}
+
+int gps_full_es_grad_tall(gps_ctx* ctx, int kind, int nfold, int num_sim, double beta,
+                          int64_t nprob, const double* X, const double* y, int64_t n, int d,
+                          const double* theta, int n_ell, const double* draws, double* value,
+                          double* fold_values, double* obj, double* grad, int* info) {
+  return grad_call(ctx, kFullTallEs,
+                   {kind, GPS_BLOCK_ES, nprob, X, y, n, d, nullptr, 0, theta, n_ell, nfold, num_sim,
+                    beta, draws, 1},
+                   obj, grad, nullptr, info, value, fold_values);
+}
+
+int gps_full_es_train_tall(gps_ctx* ctx, int kind, int nfold, int num_sim, double beta,
+                           int64_t nprob, const double* X, const double* y, int64_t n, int d,
+                           const double* theta0, int n_ell, int64_t itr, double lr,
+                           const double* Xt, const double* yt, int64_t nt, int flags,
+                           const double* draws, int64_t draw_sets, double* theta_out,
+                           double* values, double* thetas, double* obj, double* mu, double* var,
+                           double* sc, int* info, int* steps_done) {
+  return train_call(ctx, kFullTallEs,
+                    {kind, GPS_BLOCK_ES, nprob, X, y, n, d, nullptr, 0, theta0, n_ell, nfold,
+                     num_sim, beta, draws, draw_sets},
+                    itr, lr, 0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu,
+                    var, sc, info, steps_done);
 }
 
 int gps_fitc_grad_batch(gps_ctx* ctx, int objective, int64_t nprob, const double* X,

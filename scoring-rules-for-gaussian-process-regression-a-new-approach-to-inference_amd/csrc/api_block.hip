@@ -34,31 +34,11 @@ int64_t bounds_pad(const std::vector<int64_t>& bnd) {
 // new lower bound min f(β[l, u]); the new upper bound is 1 once βl ≤ 1 ≤ βu.  The lower bound then
 // grows ×6.7 per step instead of ×2.25: 12 steps instead of 20 from x0 = 8e-6.  Two unscaled
 // steps follow, which let the derivative block of the gradient pass settle.  Returns β per step.
+// The arithmetic is ns_schedule_fill's (gps_internal.h), which the batch kernels run on the device.
 std::vector<double> ns_schedule(double x0) {
-  auto f = [](double x) { return x * (3.0 - x) * (3.0 - x) / 4.0; };
-  double l = std::min(std::max(x0, 1e-300), 1.0), u = 1.0;
-  std::vector<double> beta;
-  while (1.0 - l > 4e-16 && beta.size() < 200) {
-    double b = 1.0 / u;
-    // scaled while the lower bound is small; from l = 0.5 on the unscaled step converges
-    // quadratically (scaling there only chases rounding in the bounds)
-    if (l < 0.5 && f(b * l) < f(b * u)) {  // bisect f(βl) = f(βu) on [1/u, 2.999/u]
-      double lo = 1.0 / u, hi = 2.999 / u;
-      for (int it = 0; it < 100; ++it) {
-        const double mid = 0.5 * (lo + hi);
-        if (f(mid * l) < f(mid * u)) lo = mid;
-        else hi = mid;
-      }
-      b = lo;
-    }
-    const double nl = std::min(f(b * l), f(b * u));
-    u = (b * l <= 1.0 && 1.0 <= b * u) ? 1.0 : std::max(f(b * l), f(b * u));
-    l = std::min(nl, u);
-    beta.push_back(b);
-  }
-  beta.push_back(1.0);
-  beta.push_back(1.0);
-  return beta;
+  double beta[kNsMaxSteps];
+  const int cnt = ns_schedule_fill(x0, beta, kNsMaxSteps);  // never −1 at this capacity
+  return std::vector<double>(beta, beta + cnt);
 }
 
 // Energy score of one fold, ES(m, c, shape1, y, S, β) (KF:70-101) as the scripts call it on

@@ -408,6 +408,72 @@ int64_t batch_full_tall_block_ws_doubles(int64_t n, int nfold);
 int batch_full_tall_block_steps(int64_t n);
 hipError_t launch_batch_full_tall_block(const BatchFullTallBlockParams& p, hipStream_t s);
 
+// Scaled Newton–Schulz schedule for a spectrum of C/s inside [x0, 1] (api_block.hip's comment at
+// ns_schedule has the derivation): β per step into beta[0..cap), host and device.  At most
+// kNsScaledMax scaled or unscaled steps run until the lower bound reaches 1 − 4e-16, two unscaled
+// steps follow.  Returns the step count, or −1 when it would exceed cap.
+constexpr int kNsScaledMax = 200;
+constexpr int kNsMaxSteps = kNsScaledMax + 2;  // the resident path's capacity: never exceeded
+__host__ __device__ inline double ns_poly(double x) { return x * (3.0 - x) * (3.0 - x) / 4.0; }
+__host__ __device__ inline int ns_schedule_fill(double x0, double* beta, int cap) {
+  const double xl = x0 < 1e-300 ? 1e-300 : x0;  // max(x0, 1e-300)
+  double l = 1.0 < xl ? 1.0 : xl, u = 1.0;      // min(.., 1)
+  int cnt = 0;
+  while (1.0 - l > 4e-16 && cnt < kNsScaledMax) {
+    if (cnt + 3 > cap) return -1;
+    double b = 1.0 / u;
+    // scaled while the lower bound is small; from l = 0.5 on the unscaled step converges
+    // quadratically (scaling there only chases rounding in the bounds)
+    if (l < 0.5 && ns_poly(b * l) < ns_poly(b * u)) {  // bisect f(βl) = f(βu) on [1/u, 2.999/u]
+      double lo = 1.0 / u, hi = 2.999 / u;
+      for (int it = 0; it < 100; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (ns_poly(mid * l) < ns_poly(mid * u)) lo = mid;
+        else hi = mid;
+      }
+      b = lo;
+    }
+    const double fl = ns_poly(b * l), fu = ns_poly(b * u);
+    const double nl = fu < fl ? fu : fl;
+    u = (b * l <= 1.0 && 1.0 <= b * u) ? 1.0 : (fl < fu ? fu : fl);
+    l = u < nl ? u : nl;
+    beta[cnt++] = b;
+  }
+  if (cnt + 2 > cap) return -1;
+  beta[cnt++] = 1.0;
+  beta[cnt++] = 1.0;
+  return cnt;
+}
+
+// the same batches on the block-LOO energy score (kernels_batch_full_tall_es.hip): a
+// step is a launch sequence — (A) forward and P per problem, (E) the fold work on one workgroup per
+// (problem, fold), at most 256 of them a launch, (C) the tail and the θ update per problem — and
+// the final pass is
+// launch_batch_full_tall's with no steps.  info is 0, k in 1..n (A's leading minor), n + k (a
+// fold's P_f pivot, as §26) or 2n + 1 + f (fold f's Newton–Schulz schedule needs more than
+// kBatchEsNsCap steps: σ² is below ~1e-24 of ‖Π_f‖∞).
+constexpr int kBatchEsNsCap = 40;        // Newton–Schulz steps a fold may run
+#define GPS_BATCH_ES_MAX_FOLD 128        // rows of the largest fold: two tiles on a side
+#define GPS_BATCH_ES_MAX_SIM 512
+struct BatchFullTallEsParams {
+  BatchParams b;        // b.objective is unused; b.nsteps is 0 or 1
+  double* ws;           // [nprob][ws_stride], 32-byte aligned
+  int64_t ws_stride;    // >= batch_full_tall_es_ws_doubles(n, nfold, num_sim), a multiple of 4
+  int nfold, num_sim;
+  double beta;
+  const double* draws;  // device, [nprob][draw_sets][2·num_sim·n]; step i reads set i mod draw_sets
+  int64_t draw_sets;
+  double* value;        // [nprob] BATCH_MODE_GRAD
+  double* fold_values;  // [nprob][nfold] BATCH_MODE_GRAD, or NULL
+};
+// 3·np² + 2·np + 72 + nfold·(11·bp² + 6·Sp·bp + Sp²) doubles a problem: np, bp the padded n and
+// largest fold, Sp = 64·⌈(num_sim + 1)/64⌉ (the forward iterates are recomputed, not stored)
+int64_t batch_full_tall_es_ws_doubles(int64_t n, int nfold, int num_sim);
+// one launch of the sequence: ES_FORWARD, ES_FOLDS, ES_TAIL (a step, or the one evaluation of
+// BATCH_MODE_GRAD; nothing with b.nsteps = 0) and ES_FINAL (nothing without b.do_final)
+enum { ES_FORWARD = 0, ES_FOLDS = 1, ES_TAIL = 2, ES_FINAL = 3, ES_PHASES = 4 };
+hipError_t launch_batch_full_tall_es(const BatchFullTallEsParams& p, int phase, hipStream_t s);
+
 // ------------------------------------------------------------------ launchers
 // raises `kernel`'s dynamic-LDS limit to `bytes` on the current device, once per (device, kernel)
 // (kernels_surface.hip); every launcher of a kernel that may need more than 64 KB calls it first

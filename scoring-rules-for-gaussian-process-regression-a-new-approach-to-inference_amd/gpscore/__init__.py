@@ -10,8 +10,9 @@ Drop-in layers:
                           ``fitc_*_tall`` takes FITC problems of up to n = 2048 (kin40k's n = 500),
                           ``train_tall`` / ``value_and_grad_tall`` full GPs of up to n = 512,
                           ``blockloo_train_tall`` / ``blockloo_value_and_grad_tall`` the same on
-                          the block-LOO DSS / KC objectives, ``fitc_blockloo_*_tall`` the tall
-                          FITC problems on them;
+                          the block-LOO DSS / KC objectives, ``es_train_tall`` /
+                          ``es_value_and_grad_tall`` on the block-LOO energy score,
+                          ``fitc_blockloo_*_tall`` the tall FITC problems on DSS / KC;
   * ``gpscore.dist``    — one process per GPU, FITC row sharding;
   * ``gpscore._lib``    — the ctypes binding of libgpscore.so (include/gpscore.h).
 """
@@ -19,7 +20,8 @@ from ._lib import (Context, GpsError, NotPositiveDefinite, build_id, check_build
                    default_context, load, OBJ_NAMES, SCORE_NAMES)
 from .gp import GP, FitResult, fit, pack_theta, score, surface  # noqa: F401
 from .batch import (BatchTrainResult, FitcBatchTrainResult, blockloo_train_tall,  # noqa: F401
-                    blockloo_value_and_grad_tall, fitc_blockloo_train_tall,
+                    blockloo_value_and_grad_tall, es_train_tall, es_value_and_grad_tall,
+                    fitc_blockloo_train_tall,
                     fitc_blockloo_value_and_grad_tall, fitc_train_batch,
                     fitc_train_tall, fitc_value_and_grad_batch, fitc_value_and_grad_tall,
                     train_batch, train_tall, value_and_grad_batch, value_and_grad_tall)

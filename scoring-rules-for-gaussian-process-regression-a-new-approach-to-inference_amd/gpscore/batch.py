@@ -1,6 +1,6 @@
 """Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
 (DESIGN §19, §20), and their siblings for taller problems (§22, §24; the block-LOO DSS / KC
-objectives §26 for the full GP, §27 for FITC).
+objectives §26 for the full GP, §27 for FITC; the block-LOO energy score §32).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
@@ -9,6 +9,7 @@ objectives §26 for the full GP, §27 for FITC).
                                    itr=1000, Xt=Xt, yt=yt)
     res = gpscore.train_tall(X, y, theta0, "loo_crps", lr=1.0, itr=400, Xt=Xt, yt=yt)  # n <= 512
     res = gpscore.blockloo_train_tall(X, y, theta0, "dss", nfold=4, lr=1e-3, itr=150, Xt=Xt, yt=yt)
+    res = gpscore.es_train_tall(X, y, theta0, nfold=4, num_sim=300, lr=0.1, itr=25, Xt=Xt, yt=yt)
     res = gpscore.fitc_blockloo_train_tall(X, y, Z0, theta0, "kc", nfold=4, lr=0.1, itr=3000,
                                            Xt=Xt, yt=yt)                                # n <= 2048
 
@@ -298,6 +299,116 @@ def blockloo_train_tall(X, y, theta0, objective="dss", nfold=4, lr=1e-3, itr=150
              ptr(y), n, d, ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
              GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(values), ptr(thetas),
              ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
+    return BatchTrainResult(
+        theta=theta, series={"objective": values, "theta": thetas},
+        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
+        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
+        info=info, steps_done=steps)
+
+
+BATCH_ES_MAX_FOLD = 128  # GPS_BATCH_ES_MAX_FOLD: rows of the largest fold
+BATCH_ES_MAX_SIM = 512   # GPS_BATCH_ES_MAX_SIM
+
+
+def _es_args(nfold, n, num_sim, beta):
+    nfold = _nfold(nfold, n)
+    if -(-n // nfold) > BATCH_ES_MAX_FOLD:
+        raise ValueError(f"n = {n} rows in {nfold} folds: a batched energy-score fold holds at most "
+                         f"{BATCH_ES_MAX_FOLD} rows (its square-root work has to fit one launch), "
+                         f"use more folds")
+    if isinstance(num_sim, bool) or int(num_sim) != num_sim or not 2 <= num_sim <= BATCH_ES_MAX_SIM:
+        raise ValueError(f"num_sim = {num_sim!r}: a batched energy score takes 2..{BATCH_ES_MAX_SIM} "
+                         f"draws a fold")
+    beta = float(beta)
+    if not 0.0 < beta <= 2.0:
+        raise ValueError(f"beta must be in (0, 2], got {beta!r}")
+    return nfold, int(num_sim), beta
+
+
+def _es_draws(draws, B, sets, n, nfold, num_sim, rng):
+    """(B, sets, 2·num_sim·n) draws: the caller's, or es_draws from rng problem-major then
+    set-major."""
+    from .gp import es_draws
+    per = 2 * num_sim * n
+    if draws is None:
+        rng = np.random.default_rng(rng)
+        return np.stack([np.stack([es_draws(n, nfold, num_sim, rng) for _ in range(sets)])
+                         for _ in range(B)])
+    try:
+        draws = f64(draws)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"draws must be a rectangular array: {e}") from None
+    if draws.size != B * sets * per:
+        raise ValueError(f"draws must hold B·draw_sets·2·num_sim·n = {B}·{sets}·{per} values "
+                         f"(es_draws' layout per set), got {draws.size}")
+    return np.ascontiguousarray(draws).reshape(B, sets, per)
+
+
+def es_value_and_grad_tall(X, y, theta, nfold=4, num_sim=300, beta=1.0, draws=None, rng=None,
+                           rbf=False, ctx=None):
+    """The block-LOO energy score (GP.block_loo's "es", KF:607-663) and its analytic gradient for B
+    full GPs of 1 <= n <= 512 training points at their own θ (one gps_full_es_grad_tall call,
+    DESIGN §32: the fold work runs on one workgroup per (problem, fold)).  ``draws``: (B,
+    2·num_sim·n) standard-normal draws, one es_draws set a problem (None: drawn from ``rng``,
+    problem-major).  A fold holds at most 128 rows (ceil(n / nfold) <= 128), 2 <= num_sim <= 512, 0 <
+    beta <= 2; other arguments and refusals as blockloo_value_and_grad_tall.  ``info`` n + k as
+    there, 2n + 1 + f: fold f's square root would need more than 40 Newton–Schulz steps.
+    Returns (values (B,), grads (B, 2 + n_ell), fold_values (B, nfold), objectives {name: (B,)},
+    info (B,))."""
+    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
+    B, n, d = X.shape
+    th, n_ell = _thetas(theta, B, d)
+    nfold, num_sim, beta = _es_args(nfold, n, num_sim, beta)
+    draws = _es_draws(draws, B, 1, n, nfold, num_sim, rng)
+    ctx = ctx or _lib.default_context()
+    vals, fold = np.empty(B), np.empty((B, nfold))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    grad = np.empty((B, 2 + n_ell))
+    info = np.zeros(B, np.int32)
+    ctx.call("gps_full_es_grad_tall", GPS_RBF if rbf else GPS_ARD, nfold, num_sim, beta, B, ptr(X),
+             ptr(y), n, d, ptr(th), n_ell, ptr(draws), ptr(vals), ptr(fold), ptr(obj), ptr(grad),
+             _iptr(info))
+    return vals, grad, fold, {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, info
+
+
+def es_train_tall(X, y, theta0, nfold=4, num_sim=300, beta=1.0, lr=0.1, itr=25, draws=None,
+                  draw_sets=None, rng=None, Xt=None, yt=None, rbf=False, stale_noise=False,
+                  ctx=None):
+    """train_tall on the block-LOO energy score (one gps_full_es_train_tall call): the 4-fold ES fit
+    of "kin40k-FULL-compare.py" (KF:607-732: 25 steps at lr 0.1 with 300 draws a fold, the defaults
+    here) for B problems at once.  Step i uses draw set i mod ``draw_sets``: ``draw_sets`` = itr (the
+    default) is the scripts' fresh draws every step, 1 is common random numbers; 1 <= draw_sets <=
+    max(itr, 1).  ``draws``: (B, draw_sets, 2·num_sim·n), every set in es_draws' layout (None: drawn
+    from ``rng``, problem-major then set-major).  The draws count towards the 8 GiB a call may
+    take: B = 30 with 25 sets of 300 at n = 500 is 1.8 GB and fits, B = 256 does not — fewer
+    ``draw_sets`` is the way out.  ``series["objective"]`` is the energy score before each step;
+    limits as es_value_and_grad_tall, everything else as train_tall: arguments, refusals and
+    BatchTrainResult."""
+    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
+    B, n, d = X.shape
+    th0, n_ell = _thetas(theta0, B, d)
+    nfold, num_sim, beta = _es_args(nfold, n, num_sim, beta)
+    itr, lr = _steps(itr, lr)
+    sets = max(itr, 1) if draw_sets is None else draw_sets
+    if isinstance(sets, bool) or int(sets) != sets or not 1 <= sets <= max(itr, 1):
+        raise ValueError(f"draw_sets = {draw_sets!r}: a fit of {itr} steps takes 1..{max(itr, 1)} "
+                         f"draw sets")
+    sets = int(sets)
+    Xt, yt, nt = _tests(Xt, yt, B, d)
+    draws = _es_draws(draws, B, sets, n, nfold, num_sim, rng)
+    ctx = ctx or _lib.default_context()
+    nth = 2 + n_ell
+    theta = np.empty((B, nth))
+    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
+    obj = np.empty((B, len(OBJ_NAMES)))
+    mu = np.empty((B, nt)) if nt else None
+    var = np.empty((B, nt)) if nt else None
+    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
+    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    ctx.call("gps_full_es_train_tall", GPS_RBF if rbf else GPS_ARD, nfold, num_sim, beta, B, ptr(X),
+             ptr(y), n, d, ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
+             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(draws), sets, ptr(theta), ptr(values),
+             ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
     return BatchTrainResult(
         theta=theta, series={"objective": values, "theta": thetas},
         objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,

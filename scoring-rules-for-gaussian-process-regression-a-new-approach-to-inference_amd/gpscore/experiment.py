@@ -19,8 +19,8 @@ run_fitc_batch, one fitc_train_tall call per method; its block-LOO DSS and KC fi
 run_fitc_blockloo_batch, one fitc_blockloo_train_tall call per method.  KF's
 LOO-CRPS / NLML / LOO-LogS fits (full GP, n = 500) have a batch route as well: run_full_batch, one
 train_tall call per method for all replicates; its block-LOO DSS fit goes through
-run_full_blockloo_batch, one blockloo_train_tall call for all replicates, and only its ES fit
-stays with run.
+run_full_blockloo_batch, one blockloo_train_tall call for all replicates, and its ES fit through
+run_full_es_batch, one es_train_tall call: all five KF methods have a one-call-per-method route.
 
 Every number here comes from gpscore.GP (libgpscore.so): the SGD loops are GP.train, the
 predictive and its scores GP.predict (run_simple: gpscore.batch.train_batch).  The workbook is not shipped (the scripts open it from
@@ -36,7 +36,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
-from .batch import (BLOCK_BATCH_OBJS, blockloo_train_tall, fitc_blockloo_train_tall,
+from .batch import (BLOCK_BATCH_OBJS, blockloo_train_tall, es_train_tall, fitc_blockloo_train_tall,
                     fitc_train_batch, fitc_train_tall, train_batch, train_tall)
 from .gp import GP
 
@@ -381,7 +381,7 @@ def run_full_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True
     array(TT, 2 + n_ell)}}: every method's TT full-GP fits (n = 500, the test predictive and the
     score bundle) are ONE train_tall call, one workgroup per replicate.  ``methods``
     defaults to the crps / nlml / logs entries of KF_METHODS; a method whose objective is dss or es
-    (block-LOO) raises ValueError here (dss and kc: run_full_blockloo_batch; es: run(kind="full")).
+    (block-LOO) raises ValueError here (dss and kc: run_full_blockloo_batch; es: run_full_es_batch).
     Data replicates
     and starting points are drawn in run's order — replicate-major, then method, initial_theta per
     method — so with the same ``seed``, ``reseed=True`` and the same method subset
@@ -436,8 +436,8 @@ def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, re
     array(TT, 2 + n_ell)}}: every method's TT full-GP fits on the nfold-fold block-LOO DSS (or KC)
     objective, the test predictive and the score bundle are ONE blockloo_train_tall call, one
     workgroup per replicate.  ``methods`` defaults to KF_METHODS' dss entry (KF:487-601,
-    150 steps at lr 1e-3); a method whose objective is es raises ValueError (use run(kind="full")),
-    one whose objective is pointwise raises too (use run_full_batch).  Data replicates and starting
+    150 steps at lr 1e-3); a method whose objective is es raises ValueError (its batch route is
+    run_full_es_batch), one whose objective is pointwise raises too (use run_full_batch).  Data replicates and starting
     points are drawn in run's order — replicate-major, then method, initial_theta per method — so
     with the same ``seed``, ``reseed=True`` and the same method subset run(kind="full",
     methods=subset) and this fit the same problems.  ``itr`` overrides the methods' step counts;
@@ -482,6 +482,61 @@ def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, re
                                       f"{int(res.steps_done[q])} steps")
         out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
         out[name]["theta"] = res.theta.copy()
+    return out
+
+
+def run_full_es_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
+                      stale_noise=True, num_sim=300, ctx=None, nfold=4):
+    """run_full_batch for KF's energy-score fit → {method: {metric: array(TT), "theta": array(TT,
+    2 + n_ell), "failed": array(TT, bool)}}: every method's TT full-GP fits on the nfold-fold
+    block-LOO energy score with ``num_sim`` draws a fold redrawn every step, the test predictive and
+    the score bundle are ONE es_train_tall call.  ``methods`` defaults to KF_METHODS' es
+    entry (KF:607-732, 25 steps at lr 0.1); any other objective raises ValueError (use
+    run_full_batch or run_full_blockloo_batch).  Data replicates, starting points and draws are
+    taken from the generator in run's order — replicate-major, then method: initial_theta, then
+    one es_draws set per step — so with the same ``seed``, ``reseed=True`` and the same es-only
+    method subset run(kind="full", methods=subset) and this fit the same problems with the same
+    draws.  ``itr`` overrides the methods' step counts; stale_noise as run_method.  A replicate
+    whose factorisation fails gets zero metrics as in run_method (KF:726-732)."""
+    from .gp import es_draws
+    if methods is None:
+        methods = {"es": KF_METHODS["es"]}
+    for name, meth in methods.items():
+        if meth.objective != "es":
+            route = "run_full_blockloo_batch" if meth.objective in BLOCK_BATCH_OBJS else "run_full_batch"
+            raise ValueError(f"run_full_es_batch: method {name!r} has objective {meth.objective!r}, "
+                             f"not 'es'; use {route} for it")
+    if int(TT) != TT or TT < 1:
+        raise ValueError(f"TT must be a positive integer, got {TT!r}")
+    TT = int(TT)
+    rng = np.random.default_rng(seed)
+    rs = None if reseed else random.Random()
+    n_pool = sheets["trainx"].shape[0]
+    steps = {name: meth.itr if itr is None else int(itr) for name, meth in methods.items()}
+    data, th0, draws = [], {name: [] for name in methods}, {name: [] for name in methods}
+    for j in range(TT):
+        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
+        data.append(dd)
+        n, d = dd["train_x"].shape
+        for name, meth in methods.items():
+            k, ell, noise = initial_theta(meth, d, rng)
+            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
+            draws[name].append(np.stack([es_draws(n, nfold, num_sim, rng)
+                                         for _ in range(max(steps[name], 1))]))
+    X = np.stack([dd["train_x"] for dd in data])
+    y = np.stack([dd["train_y"] for dd in data])
+    Xt = np.stack([dd["test_x"] for dd in data])
+    yt = np.stack([dd["test_y"] for dd in data])
+    out = {}
+    for name, meth in methods.items():
+        res = es_train_tall(X, y, np.stack(th0[name]), nfold=nfold, num_sim=num_sim, lr=meth.lr,
+                            itr=steps[name], draws=np.stack(draws[name]),
+                            draw_sets=max(steps[name], 1), Xt=Xt, yt=yt, stale_noise=stale_noise,
+                            ctx=ctx)
+        failed = np.asarray(res.info) != 0
+        out[name] = {k: np.where(failed, 0.0, res.scores["test_" + k]) for k in METRICS}
+        out[name]["theta"] = res.theta.copy()
+        out[name]["failed"] = failed
     return out
 
 
