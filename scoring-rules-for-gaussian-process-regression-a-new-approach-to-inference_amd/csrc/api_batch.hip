@@ -100,7 +100,7 @@ const Path<BatchParams> kFullTallBlock = {
     GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_block_grad",
     "batch_full_tall_block_train",
     [](int64_t n, int, int nfold, int) { return batch_full_tall_block_ws_doubles(n, nfold); }, true,
-    batch_full_tall_block_steps,
+    batch_full_tall_steps,
     [](gps_ctx*, const BatchParams& p, double* ws, int64_t stride, const Block& b,
        hipStream_t s) {
       return launch_batch_full_tall_block(

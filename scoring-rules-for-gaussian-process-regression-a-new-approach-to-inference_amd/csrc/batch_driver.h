@@ -9,6 +9,7 @@
 // the list of what therefore stayed in the kernels are in DESIGN §25): pass p by value, t from the
 // caller, and derive nth, d and m from p inside.  Included once per kernel file; everything sits
 // in that file's anonymous namespace.  The FITC pair's own GRAD-mode end is in batch_fitc_shared.h.
+// fold_begin is the fold geometry of the three block-LOO kernel files.
 #pragma once
 #include <type_traits>
 
@@ -20,6 +21,11 @@ namespace gps {
 namespace {
 
 __device__ __forceinline__ double batch_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// fold f's first row: the block-LOO paths' folds are [⌊f·n/k⌋, ⌊(f+1)·n/k⌋) (KF:496-499)
+__device__ __forceinline__ int fold_begin(int f, int n, int nfold) {
+  return (int)((int64_t)f * n / nfold);
+}
 
 // A step's prologue, between two barriers: θ → sf², σ² and 1/ℓ_k into il (GPS_ARD: exp(−b_k);
 // GPS_RBF: exp(−b/2); the FITC kernels pass GPS_ARD).  The final pass (fin) with stale_noise takes

@@ -1,6 +1,7 @@
-// What the two tall full-GP batch kernels share: kernels_batch_full_tall.hip (the pointwise
-// objectives) and kernels_batch_full_tall_block.hip (the block-LOO objectives, §26).
-// Included once by each of the two files; everything sits in that file's anonymous namespace.
+// What the tall full-GP batch kernels share: kernels_batch_full_tall.hip (the pointwise
+// objectives), kernels_batch_full_tall_block.hip (the block-LOO DSS / KC objectives,
+// §26) and kernels_batch_full_tall_es.hip (the block-LOO energy score, §32).
+// Included once by each of the three files; everything sits in that file's anonymous namespace.
 //
 // Batches of full GPs of up to GPS_BATCH_FULL_TALL_MAX_N = 512 training rows, one workgroup of 256
 // threads per problem: kernels_batch.hip's evaluation, SGD loop and final pass step
@@ -80,6 +81,46 @@ __device__ __forceinline__ Lds carve(double* sm, int np) {
   s.sh = s.sw + 2 * T;
   s.th = s.sh + BG * 16;
   return s;
+}
+
+// n rounded up to whole tiles
+__host__ __device__ inline int64_t padded(int64_t n) { return T * ((n + T - 1) / T); }
+
+// what the three launchers check alike: the problem's shape, the steps of one launch (`steps`: the
+// path's rule, asked only once n is known to be in range) and the workspace
+inline bool full_tall_args_ok(const BatchParams& p, int (*steps)(int64_t n), const double* ws,
+                              int64_t ws_stride, int64_t ws_need) {
+  return p.n >= 1 && p.n <= GPS_BATCH_FULL_TALL_MAX_N && p.d >= 1 && p.d <= GPS_BATCH_MAX_D &&
+         p.nprob >= 1 && (p.n_ell == 1 || p.n_ell == p.d) && p.nsteps >= 0 &&
+         p.nsteps <= steps(p.n) && ws && ws_stride >= ws_need && !(ws_stride & 3) &&
+         !(reinterpret_cast<uintptr_t>(ws) & 31);
+}
+
+// ------------------------------------------------------------------ the fold geometry (§26, §32)
+// the tile-aligned column range [klo, khi) that the folds of row tile bi's live rows cover
+__device__ __forceinline__ void fold_span(int bi, int n, int nfold, int& klo, int& khi) {
+  const int r0 = bi * T, r1 = min(n, r0 + T) - 1;
+  int lo = 0, hi = n;
+  for (int f = 0; f < nfold; ++f) {
+    const int a = fold_begin(f, n, nfold), b = fold_begin(f + 1, n, nfold);
+    if (a <= r0 && r0 < b) lo = a;
+    if (a <= r1 && r1 < b) hi = b;
+  }
+  klo = lo / T * T;
+  khi = (hi + T - 1) / T * T;
+}
+
+// Gblk's zeros: every tile column a row tile's folds touch (ld, nb and t from the caller: §25)
+__device__ __forceinline__ void gblk_zero(double* W2, int n, int nfold, int64_t ld, int nb, int t) {
+  for (int bi = 0; bi < nb; ++bi) {
+    int klo, khi;
+    fold_span(bi, n, nfold, klo, khi);
+    const int wd = khi - klo;
+    for (int e = t; e < T * wd; e += BT) {
+      const int i = e / wd, j = e - i * wd;
+      W2[(bi * T + i) * ld + klo + j] = 0.0;
+    }
+  }
 }
 
 // ------------------------------------------------------------------ the tile product

@@ -402,10 +402,8 @@ struct BatchFullTallBlockParams {
   double* value;        // [nprob] BATCH_MODE_GRAD: the block objective
   double* fold_values;  // [nprob][nfold] BATCH_MODE_GRAD: each fold's term, or NULL
 };
-size_t batch_full_tall_block_lds_bytes(int n);  // batch_full_tall_lds_bytes(n): no new LDS
+// LDS is batch_full_tall_lds_bytes(n) and a launch runs batch_full_tall_steps(n) steps: §24's
 int64_t batch_full_tall_block_ws_doubles(int64_t n, int nfold);
-// SGD steps one launch may run, batch_full_tall_steps' rule: a function of n alone
-int batch_full_tall_block_steps(int64_t n);
 hipError_t launch_batch_full_tall_block(const BatchFullTallBlockParams& p, hipStream_t s);
 
 // Scaled Newton–Schulz schedule for a spectrum of C/s inside [x0, 1] (api_block.hip's comment at

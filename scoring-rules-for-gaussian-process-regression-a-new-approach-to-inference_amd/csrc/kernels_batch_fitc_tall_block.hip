@@ -92,11 +92,6 @@ __device__ __forceinline__ Ws carve_ws(double* w, int n, int m, int ld, int nfol
   return s;
 }
 
-// fold f's first row
-__device__ __forceinline__ int fold_begin(int f, int n, int nfold) {
-  return (int)((int64_t)f * n / nfold);
-}
-
 // wgram_acc's two-array sibling: out[j][l] (+)= Σ_i A[i][j]·B[i][l]·w[i] (WEIGHT) or Σ_i A[i][j]·
 // B[i][l] over the chunk's rows, the same lanes and the same order
 template <bool WEIGHT>

@@ -14,8 +14,6 @@ __global__ __launch_bounds__(BT) void batch_full_tall_kernel(BatchFullTallParams
   tall_body<false>(tp.b, tp.ws, tp.ws_stride, 0, 0, nullptr, nullptr);
 }
 
-int padded(int64_t n) { return T * (int)((n + T - 1) / T); }
-
 }  // namespace
 
 size_t batch_full_tall_lds_bytes(int n) {
@@ -35,11 +33,8 @@ int batch_full_tall_steps(int64_t n) {
 
 hipError_t launch_batch_full_tall(const BatchFullTallParams& tp, hipStream_t s) {
   const BatchParams& p = tp.b;
-  if (p.n < 1 || p.n > GPS_BATCH_FULL_TALL_MAX_N || p.d < 1 || p.d > GPS_BATCH_MAX_D ||
-      p.nprob < 1 || (p.n_ell != 1 && p.n_ell != p.d) || p.nsteps < 0 ||
-      p.nsteps > batch_full_tall_steps(p.n) || !tp.ws ||
-      tp.ws_stride < batch_full_tall_ws_doubles(p.n) || (tp.ws_stride & 3) ||
-      (reinterpret_cast<uintptr_t>(tp.ws) & 31))
+  if (!full_tall_args_ok(p, batch_full_tall_steps, tp.ws, tp.ws_stride,
+                         batch_full_tall_ws_doubles(p.n)))
     return hipErrorInvalidValue;
   const hipError_t e = raise_dynamic_lds((const void*)batch_full_tall_kernel,
                                          batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));

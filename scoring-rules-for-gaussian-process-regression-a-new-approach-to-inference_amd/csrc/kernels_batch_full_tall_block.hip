@@ -30,24 +30,6 @@ namespace gps {
 
 namespace {
 
-// fold f's first row
-__device__ __forceinline__ int fold_begin(int f, int n, int nfold) {
-  return (int)((int64_t)f * n / nfold);
-}
-
-// the tile-aligned column range [klo, khi) that the folds of row tile bi's live rows cover
-__device__ __forceinline__ void fold_span(int bi, int n, int nfold, int& klo, int& khi) {
-  const int r0 = bi * T, r1 = min(n, r0 + T) - 1;
-  int lo = 0, hi = n;
-  for (int f = 0; f < nfold; ++f) {
-    const int a = fold_begin(f, n, nfold), b = fold_begin(f + 1, n, nfold);
-    if (a <= r0 && r0 < b) lo = a;
-    if (a <= r1 && r1 < b) hi = b;
-  }
-  klo = lo / T * T;
-  khi = (hi + T - 1) / T * T;
-}
-
 __device__ __forceinline__ int block_gradient(const Lds& s, const double* x, double* W0,
                                               double* W1, double* W2, int n, int np, int d,
                                               int objective, int nfold, double sf2,
@@ -61,16 +43,7 @@ __device__ __forceinline__ int block_gradient(const Lds& s, const double* x, dou
   double* gc = s.ct;    // fold-local: the CRPS variance derivative, zero in the fold's padding
   double* gm = s.v;     // the CRPS mean derivative at the fold's global rows
   gram_lower(s, W1, W0, ld, nb);  // P = XᵀX; X is dead from here on
-  // Gblk's zeros: every tile column a row tile's folds touch
-  for (int bi = 0; bi < nb; ++bi) {
-    int klo, khi;
-    fold_span(bi, n, nfold, klo, khi);
-    const int wd = khi - klo;
-    for (int e = t; e < T * wd; e += BT) {
-      const int i = e / wd, j = e - i * wd;
-      W2[(bi * T + i) * ld + klo + j] = 0.0;
-    }
-  }
+  gblk_zero(W2, n, nfold, ld, nb, t);
   __syncthreads();
   value = 0.0;
   for (int f = 0; f < nfold; ++f) {
@@ -192,8 +165,6 @@ __global__ __launch_bounds__(BT) void batch_full_tall_block_kernel(BatchFullTall
   tall_body<true>(tp.b, tp.ws, tp.ws_stride, tp.nfold, tp.w1, tp.value, tp.fold_values);
 }
 
-int64_t padded(int64_t n) { return T * ((n + T - 1) / T); }
-
 // W1's doubles: X, then the fold scratch, then Y
 int64_t w1_doubles(int64_t n, int nfold) {
   const int64_t np = padded(n), bp = padded((n + nfold - 1) / nfold);
@@ -202,37 +173,27 @@ int64_t w1_doubles(int64_t n, int nfold) {
 
 }  // namespace
 
-size_t batch_full_tall_block_lds_bytes(int n) { return batch_full_tall_lds_bytes(n); }
-
 int64_t batch_full_tall_block_ws_doubles(int64_t n, int nfold) {
   const int64_t np = padded(n);
   return 2 * np * np + w1_doubles(n, nfold);
 }
 
-int batch_full_tall_block_steps(int64_t n) {
-  const int64_t nb = padded(n) / T;
-  const int64_t s = 1024 / (nb * nb * nb);
-  return (int)(s < 1 ? 1 : s > kBatchStepsPerLaunch ? kBatchStepsPerLaunch : s);
-}
-
 hipError_t launch_batch_full_tall_block(const BatchFullTallBlockParams& tq, hipStream_t s) {
   BatchFullTallBlockParams tp = tq;
   const BatchParams& p = tp.b;
-  if (p.n < 1 || p.n > GPS_BATCH_FULL_TALL_MAX_N || p.d < 1 || p.d > GPS_BATCH_MAX_D ||
-      p.nprob < 1 || (p.n_ell != 1 && p.n_ell != p.d) || p.nsteps < 0 ||
-      p.nsteps > batch_full_tall_block_steps(p.n) || tp.nfold < 2 ||
-      tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
-      (p.objective != GPS_BLOCK_DSS && p.objective != GPS_BLOCK_KC) || !tp.ws ||
-      tp.ws_stride < batch_full_tall_block_ws_doubles(p.n, tp.nfold) || (tp.ws_stride & 3) ||
-      (reinterpret_cast<uintptr_t>(tp.ws) & 31) || (p.mode == BATCH_MODE_GRAD && !tp.value))
+  // (the fold count first: the workspace size divides by it)
+  if (tp.nfold < 2 || tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
+      (p.objective != GPS_BLOCK_DSS && p.objective != GPS_BLOCK_KC) ||
+      (p.mode == BATCH_MODE_GRAD && !tp.value) ||
+      !full_tall_args_ok(p, batch_full_tall_steps, tp.ws, tp.ws_stride,
+                         batch_full_tall_block_ws_doubles(p.n, tp.nfold)))
     return hipErrorInvalidValue;
   tp.w1 = w1_doubles(p.n, tp.nfold);
-  const hipError_t e =
-      raise_dynamic_lds((const void*)batch_full_tall_block_kernel,
-                        batch_full_tall_block_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
+  const hipError_t e = raise_dynamic_lds((const void*)batch_full_tall_block_kernel,
+                                         batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(batch_full_tall_block_kernel, dim3((unsigned)p.nprob), dim3(BT),
-                     batch_full_tall_block_lds_bytes(p.n), s, tp);
+                     batch_full_tall_lds_bytes(p.n), s, tp);  // §24's LDS layout unchanged
   return hipGetLastError();
 }
 

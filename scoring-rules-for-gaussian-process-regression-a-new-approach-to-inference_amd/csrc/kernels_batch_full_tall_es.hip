@@ -35,8 +35,6 @@ namespace {
 constexpr int kVec = 72;  // obj 8 | fold values 32 | fold info 32
 constexpr int kEsFoldWgs = 256;  // fold workgroups a launch holds: the MI355X's compute units
 
-__host__ __device__ inline int64_t padT(int64_t n) { return T * ((n + T - 1) / T); }
-
 struct EsShape {
   int np, bp, Sp;
   int64_t vec, fws, stride;
@@ -44,30 +42,13 @@ struct EsShape {
 
 __host__ __device__ inline EsShape es_shape(int n, int nfold, int S) {
   EsShape e;
-  e.np = (int)padT(n);
-  e.bp = (int)padT((n + nfold - 1) / nfold);
-  e.Sp = (int)padT(S + 1);
+  e.np = (int)padded(n);
+  e.bp = (int)padded((n + nfold - 1) / nfold);
+  e.Sp = (int)padded(S + 1);
   e.vec = 3 * (int64_t)e.np * e.np;
   e.fws = 11 * (int64_t)e.bp * e.bp + 6 * (int64_t)e.Sp * e.bp + (int64_t)e.Sp * e.Sp;
   e.stride = e.vec + 2 * e.np + kVec + nfold * e.fws;
   return e;
-}
-
-__device__ __forceinline__ int fold_begin(int f, int n, int nfold) {
-  return (int)((int64_t)f * n / nfold);
-}
-
-// the tile-aligned column range [klo, khi) that the folds of row tile bi's live rows cover
-__device__ __forceinline__ void fold_span(int bi, int n, int nfold, int& klo, int& khi) {
-  const int r0 = bi * T, r1 = min(n, r0 + T) - 1;
-  int lo = 0, hi = n;
-  for (int f = 0; f < nfold; ++f) {
-    const int a = fold_begin(f, n, nfold), b = fold_begin(f + 1, n, nfold);
-    if (a <= r0 && r0 < b) lo = a;
-    if (a <= r1 && r1 < b) hi = b;
-  }
-  klo = lo / T * T;
-  khi = (hi + T - 1) / T * T;
 }
 
 // θ of problem pb into LDS, then sf², σ² and 1/ℓ_k: step_prologue's arithmetic
@@ -108,15 +89,7 @@ __global__ __launch_bounds__(BT) void es_forward_kernel(BatchFullTallEsParams tp
     return;
   }
   gram_lower(s, W1, W0, ld, nb);  // P = XᵀX; X is dead from here on
-  for (int bi = 0; bi < nb; ++bi) {  // Gblk's zeros: every tile column a row tile's folds touch
-    int klo, khi;
-    fold_span(bi, n, tp.nfold, klo, khi);
-    const int wd = khi - klo;
-    for (int e = t; e < T * wd; e += BT) {
-      const int i = e / wd, j = e - i * wd;
-      W2[(bi * T + i) * ld + klo + j] = 0.0;
-    }
-  }
+  gblk_zero(W2, n, tp.nfold, ld, nb, t);
   for (int e = t; e < np; e += BT) vec[e] = e < n ? s.alpha[e] : 0.0;
   if (t == 0)
     for (int q = 0; q < GPS_N_OBJ; ++q) vec[2 * np + q] = obj[q];
@@ -190,7 +163,7 @@ __global__ __launch_bounds__(BT) void es_fold_kernel(BatchFullTallEsParams tp, i
   const int np = sh.np, Sp = sh.Sp, nS = Sp / T;
   const Lds s = carve(sm, max(sh.bp, Sp));
   const int a = fold_begin(f, n, nfold), bs = fold_begin(f + 1, n, nfold) - a;
-  const int bq = (int)padT(bs), nbf = bq / T;
+  const int bq = (int)padded(bs), nbf = bq / T;
   const int64_t ld = np, b2 = (int64_t)bq * bq, sb = (int64_t)Sp * bq;
   double* W0 = tp.ws + pb * tp.ws_stride;
   double* W2 = W0 + 2 * ld * ld;
@@ -548,16 +521,15 @@ int64_t batch_full_tall_es_ws_doubles(int64_t n, int nfold, int num_sim) {
 
 hipError_t launch_batch_full_tall_es(const BatchFullTallEsParams& tp, int phase, hipStream_t s) {
   const BatchParams& p = tp.b;
-  if (p.n < 1 || p.n > GPS_BATCH_FULL_TALL_MAX_N || p.d < 1 || p.d > GPS_BATCH_MAX_D ||
-      p.nprob < 1 || (p.n_ell != 1 && p.n_ell != p.d) || p.nsteps < 0 || p.nsteps > 1 ||
-      tp.nfold < 2 || tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
+  // (the fold count first: the workspace size divides by it; a step is a launch sequence, so a
+  // launch runs at most one)
+  if (tp.nfold < 2 || tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
       (p.n + tp.nfold - 1) / tp.nfold > GPS_BATCH_ES_MAX_FOLD || tp.num_sim < 2 ||
       tp.num_sim > GPS_BATCH_ES_MAX_SIM || !(tp.beta > 0.0 && tp.beta <= 2.0) || !tp.draws ||
-      tp.draw_sets < 1 || !tp.ws ||
-      tp.ws_stride < batch_full_tall_es_ws_doubles(p.n, tp.nfold, tp.num_sim) ||
-      (tp.ws_stride & 3) || (reinterpret_cast<uintptr_t>(tp.ws) & 31) ||
-      (int64_t)p.nprob * tp.nfold > (int64_t)1 << 30 ||
-      (p.mode == BATCH_MODE_GRAD && !tp.value) || phase < 0 || phase >= ES_PHASES)
+      tp.draw_sets < 1 || (int64_t)p.nprob * tp.nfold > (int64_t)1 << 30 ||
+      (p.mode == BATCH_MODE_GRAD && !tp.value) || phase < 0 || phase >= ES_PHASES ||
+      !full_tall_args_ok(p, [](int64_t) { return 1; }, tp.ws, tp.ws_stride,
+                         batch_full_tall_es_ws_doubles(p.n, tp.nfold, tp.num_sim)))
     return hipErrorInvalidValue;
   const EsShape sh = es_shape(p.n, tp.nfold, tp.num_sim);
   const size_t lds_n = batch_full_tall_lds_bytes(p.n);
@@ -568,7 +540,7 @@ hipError_t launch_batch_full_tall_es(const BatchFullTallEsParams& tp, int phase,
       (e = raise_dynamic_lds((const void*)es_tail_kernel,
                              batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N))) != hipSuccess ||
       (e = raise_dynamic_lds((const void*)es_fold_kernel,
-                             es_fold_lds_bytes((int)padT(GPS_BATCH_ES_MAX_SIM + 1)))) != hipSuccess)
+                             es_fold_lds_bytes((int)padded(GPS_BATCH_ES_MAX_SIM + 1)))) != hipSuccess)
     return e;
   if (phase == ES_FINAL) {  // §24's final pass: its kernel with no steps
     if (p.mode != BATCH_MODE_TRAIN || !p.do_final) return hipSuccess;

@@ -49,6 +49,9 @@ BATCH_MAX_N, BATCH_MAX_D = 128, 16  # GPS_SURFACE_MAX_N, GPS_BATCH_MAX_D
 BATCH_FITC_MAX_M = 32  # GPS_BATCH_FITC_MAX_M
 BATCH_FITC_TALL_MAX_N = 2048  # GPS_BATCH_FITC_TALL_MAX_N
 BATCH_FULL_TALL_MAX_N = 512  # GPS_BATCH_FULL_TALL_MAX_N
+BATCH_BLOCK_MAX_FOLDS = 32  # GPS_BATCH_BLOCK_MAX_FOLDS
+BATCH_ES_MAX_FOLD = 128  # GPS_BATCH_ES_MAX_FOLD: rows of the largest fold
+BATCH_ES_MAX_SIM = 512  # GPS_BATCH_ES_MAX_SIM
 SCORE_NAMES = ("test_crps", "test_logs", "test_msll", "test_smse", "test_mse", "test_cover")
 
 _c_int, _c_i64, _c_dbl, _c_vp, _c_cp = (ctypes.c_int, ctypes.c_int64, ctypes.c_double,

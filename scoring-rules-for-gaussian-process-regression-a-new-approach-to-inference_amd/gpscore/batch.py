@@ -33,14 +33,17 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _lib
-from ._lib import (BATCH_FITC_MAX_M, BATCH_FITC_TALL_MAX_N, BATCH_FULL_TALL_MAX_N, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD, GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES,
-                   SCORE_NAMES, f64, ptr)
+from ._lib import (BATCH_BLOCK_MAX_FOLDS, BATCH_ES_MAX_FOLD, BATCH_ES_MAX_SIM, BATCH_FITC_MAX_M,
+                   BATCH_FITC_TALL_MAX_N, BATCH_FULL_TALL_MAX_N, BATCH_MAX_D, BATCH_MAX_N, GPS_ARD,
+                   GPS_BATCH_STALE_NOISE, GPS_RBF, OBJ_NAMES, SCORE_NAMES, f64, ptr)
 
 BATCH_OBJS = OBJ_NAMES[:3]  # nlml, loo_crps, loo_logs
+BLOCK_BATCH_OBJS = ["dss", "kc"]  # GPS_BLOCK_DSS, GPS_BLOCK_KC
 _PI = ctypes.POINTER(ctypes.c_int32)
 
 
@@ -100,27 +103,71 @@ def _objective(objective):
     return OBJ_NAMES.index(objective)
 
 
-def _full_value_and_grad(entry, max_n, X, y, theta, objective, rbf, ctx):
-    X, y = _problems(X, y, max_n)
-    B, n, d = X.shape
-    th, n_ell = _thetas(theta, B, d)
-    code = _objective(objective)
-    ctx = ctx or _lib.default_context()
-    obj = np.empty((B, len(OBJ_NAMES)))
-    grad = np.empty((B, 2 + n_ell))
-    info = np.zeros(B, np.int32)
-    ctx.call(entry, GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
-             ptr(th), n_ell, ptr(obj), ptr(grad), _iptr(info))
-    objs = {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
-    return objs[objective], grad, objs, info
+def _block_objective(objective):
+    if objective not in BLOCK_BATCH_OBJS:
+        raise ValueError(f"objective must be one of {BLOCK_BATCH_OBJS} (the pointwise objectives go "
+                         f"through train_tall, the energy score through GP.block_loo), got "
+                         f"{objective!r}")
+    return BLOCK_BATCH_OBJS.index(objective)
 
 
-def value_and_grad_batch(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
-    """Objective value and analytic gradient of B small full GPs at their own θ (one
-    gps_full_grad_batch call; per problem what GP.value_and_grad returns).  Returns
-    (values (B,), grads (B, 2 + n_ell), objectives {name: (B,)}, info (B,))."""
-    return _full_value_and_grad("gps_full_grad_batch", BATCH_MAX_N, X, y, theta, objective, rbf,
-                                ctx)
+def _nfold(nfold, n):
+    hi = min(n, BATCH_BLOCK_MAX_FOLDS)
+    if isinstance(nfold, bool) or int(nfold) != nfold or not 2 <= nfold <= hi:
+        raise ValueError(f"nfold = {nfold!r}: a batched block-LOO problem of n = {n} rows has "
+                         f"2..{hi} folds")
+    return int(nfold)
+
+
+def _es_args(nfold, n, num_sim, beta):
+    nfold = _nfold(nfold, n)
+    if -(-n // nfold) > BATCH_ES_MAX_FOLD:
+        raise ValueError(f"n = {n} rows in {nfold} folds: a batched energy-score fold holds at most "
+                         f"{BATCH_ES_MAX_FOLD} rows (its square-root work has to fit one launch), "
+                         f"use more folds")
+    if isinstance(num_sim, bool) or int(num_sim) != num_sim or not 2 <= num_sim <= BATCH_ES_MAX_SIM:
+        raise ValueError(f"num_sim = {num_sim!r}: a batched energy score takes 2..{BATCH_ES_MAX_SIM} "
+                         f"draws a fold")
+    beta = float(beta)
+    if not 0.0 < beta <= 2.0:
+        raise ValueError(f"beta must be in (0, 2], got {beta!r}")
+    return nfold, int(num_sim), beta
+
+
+def _es_draws(draws, B, sets, n, nfold, num_sim, rng):
+    """(B, sets, 2·num_sim·n) draws: the caller's, or es_draws from rng problem-major then
+    set-major."""
+    from .gp import es_draws
+    per = 2 * num_sim * n
+    if draws is None:
+        rng = np.random.default_rng(rng)
+        return np.stack([np.stack([es_draws(n, nfold, num_sim, rng) for _ in range(sets)])
+                         for _ in range(B)])
+    try:
+        draws = f64(draws)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"draws must be a rectangular array: {e}") from None
+    if draws.size != B * sets * per:
+        raise ValueError(f"draws must hold B·draw_sets·2·num_sim·n = {B}·{sets}·{per} values "
+                         f"(es_draws' layout per set), got {draws.size}")
+    return np.ascontiguousarray(draws).reshape(B, sets, per)
+
+
+def _inducing(Z, B, d):
+    """Z (B, m, d) checked against the batch and the kernel's limit."""
+    try:
+        Z = f64(Z)
+    except (ValueError, TypeError) as e:  # a ragged list of inducing sets
+        raise ValueError(f"Z must be a rectangular array, one m per batch: {e}") from None
+    if Z.ndim == 2 and d == 1:
+        Z = Z[:, :, None]
+    if Z.ndim != 3 or Z.shape[0] != B or Z.shape[2] != d:
+        raise ValueError(f"Z must be (B, m, d) = ({B}, m, {d}) (or (B, m) when d = 1), got {Z.shape}")
+    m = Z.shape[1]
+    if not 1 <= m <= BATCH_FITC_MAX_M:
+        raise ValueError(f"m = {m}: a batched FITC problem holds 1..{BATCH_FITC_MAX_M} inducing "
+                         f"inputs")
+    return np.ascontiguousarray(Z), m
 
 
 @dataclass
@@ -174,31 +221,135 @@ def _tests(Xt, yt, B, d):
     return Xt, yt, nt
 
 
-def _full_train(entry, max_n, X, y, theta0, objective, lr, itr, Xt, yt, rbf, stale_noise, ctx):
-    X, y = _problems(X, y, max_n)
+@dataclass
+class FitcBatchTrainResult(BatchTrainResult):
+    """fitc_train_batch's outputs: BatchTrainResult's fields and ``Z`` (B, m, d), the final
+    inducing inputs.  ``info`` is 0, k in 1..m (K(Z,Z) + 1e-3·I's leading minor) or m + k (B's)."""
+    Z: np.ndarray = None
+
+
+@dataclass(frozen=True)
+class _Path:
+    """One batch path, as api_batch.hip's Path<P>: its two entry points, its limit on n, whether
+    the model is FITC (Z and m in the call, no kernel kind) and its objective rule — "point": one
+    of BATCH_OBJS; "block": one of BLOCK_BATCH_OBJS over nfold folds; "es": the energy score over
+    nfold folds with num_sim draws and β."""
+    grad: str
+    train: str
+    max_n: int
+    fitc: bool = False
+    rule: str = "point"
+
+
+_FULL = _Path("gps_full_grad_batch", "gps_full_train_batch", BATCH_MAX_N)
+_FULL_TALL = _Path("gps_full_grad_tall", "gps_full_train_tall", BATCH_FULL_TALL_MAX_N)
+_FULL_BLOCK = _Path("gps_full_blockloo_grad_tall", "gps_full_blockloo_train_tall",
+                    BATCH_FULL_TALL_MAX_N, rule="block")
+_FULL_ES = _Path("gps_full_es_grad_tall", "gps_full_es_train_tall", BATCH_FULL_TALL_MAX_N,
+                 rule="es")
+_FITC = _Path("gps_fitc_grad_batch", "gps_fitc_train_batch", BATCH_MAX_N, fitc=True)
+_FITC_TALL = _Path("gps_fitc_grad_tall", "gps_fitc_train_tall", BATCH_FITC_TALL_MAX_N, fitc=True)
+_FITC_BLOCK = _Path("gps_fitc_blockloo_grad_tall", "gps_fitc_blockloo_train_tall",
+                    BATCH_FITC_TALL_MAX_N, fitc=True, rule="block")
+
+
+def _front(path, X, y, Z, theta, objective, nfold, num_sim, beta, rbf):
+    """The checks every call starts with, in their order — problems, Z, θ, the objective or the ES
+    triple, nfold — and ``lead``, the call's arguments up to n_ell (the pointers in it keep their
+    arrays alive)."""
+    X, y = _problems(X, y, path.max_n)
     B, n, d = X.shape
-    th0, n_ell = _thetas(theta0, B, d)
-    code = _objective(objective)
-    itr, lr = _steps(itr, lr)
-    Xt, yt, nt = _tests(Xt, yt, B, d)
+    m = 0
+    if path.fitc:
+        Z, m = _inducing(Z, B, d)
+    th, n_ell = _thetas(theta, B, d)
+    if path.rule == "es":
+        nfold, num_sim, beta = head = _es_args(nfold, n, num_sim, beta)
+    elif path.rule == "block":
+        code = _block_objective(objective)
+        nfold = _nfold(nfold, n)
+        head = (code, nfold)
+    else:
+        head = (_objective(objective),)
+    lead = (() if path.fitc else (GPS_RBF if rbf else GPS_ARD,)) + head \
+        + (B, ptr(X), ptr(y), n, d) + ((ptr(Z), m) if path.fitc else ()) + (ptr(th), n_ell)
+    return SimpleNamespace(lead=lead, B=B, n=n, d=d, m=m, n_ell=n_ell, nfold=nfold,
+                           num_sim=num_sim)
+
+
+def _objectives(obj):
+    return {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
+
+
+def _grad(path, X, y, Z, theta, objective=None, nfold=None, num_sim=None, beta=None, draws=None,
+          rng=None, rbf=False, ctx=None):
+    """A path's value + gradient call: (values, grads[, grad_Z][, fold_values], objectives, info);
+    ``values`` is the call's own output on the block and ES paths, objectives[objective] else."""
+    f = _front(path, X, y, Z, theta, objective, nfold, num_sim, beta, rbf)
+    B, es, folds = f.B, path.rule == "es", path.rule != "point"
+    if es:
+        draws = _es_draws(draws, B, 1, f.n, f.nfold, f.num_sim, rng)
     ctx = ctx or _lib.default_context()
-    nth = 2 + n_ell
+    vals, fold = (np.empty(B), np.empty((B, f.nfold))) if folds else (None, None)
+    obj = np.empty((B, len(OBJ_NAMES)))
+    grad = np.empty((B, 2 + f.n_ell))
+    gz = np.empty((B, f.m, f.d)) if path.fitc else None
+    info = np.zeros(B, np.int32)
+    ctx.call(path.grad, *f.lead, *((ptr(draws),) if es else ()),
+             *((ptr(vals), ptr(fold)) if folds else ()), ptr(obj), ptr(grad),
+             *((ptr(gz),) if path.fitc else ()), _iptr(info))
+    objs = _objectives(obj)
+    return (vals if folds else objs[objective], grad) + ((gz,) if path.fitc else ()) \
+        + ((fold,) if folds else ()) + (objs, info)
+
+
+def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, beta=None, lr=1.0,
+           lr_z=None, itr=400, draws=None, draw_sets=None, rng=None, Xt=None, yt=None, rbf=False,
+           stale_noise=False, ctx=None):
+    """A path's training call: BatchTrainResult, or FitcBatchTrainResult on a FITC path."""
+    f = _front(path, X, y, Z0, theta0, objective, nfold, num_sim, beta, rbf)
+    B, es = f.B, path.rule == "es"
+    itr, lr = _steps(itr, lr)
+    if path.fitc:
+        lr_z = lr if lr_z is None else float(lr_z)
+        if not np.isfinite(lr_z):
+            raise ValueError(f"lr_z must be finite, got {lr_z!r}")
+    if es:
+        sets = max(itr, 1) if draw_sets is None else draw_sets
+        if isinstance(sets, bool) or int(sets) != sets or not 1 <= sets <= max(itr, 1):
+            raise ValueError(f"draw_sets = {draw_sets!r}: a fit of {itr} steps takes 1..{max(itr, 1)} "
+                             f"draw sets")
+        sets = int(sets)
+    Xt, yt, nt = _tests(Xt, yt, B, f.d)
+    if es:
+        draws = _es_draws(draws, B, sets, f.n, f.nfold, f.num_sim, rng)
+    ctx = ctx or _lib.default_context()
+    nth = 2 + f.n_ell
     theta = np.empty((B, nth))
+    Z = np.empty((B, f.m, f.d)) if path.fitc else None
     values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
     obj = np.empty((B, len(OBJ_NAMES)))
     mu = np.empty((B, nt)) if nt else None
     var = np.empty((B, nt)) if nt else None
     sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
     info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call(entry, GPS_RBF if rbf else GPS_ARD, code, B, ptr(X), ptr(y), n, d,
-             ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
-             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(values), ptr(thetas),
-             ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
-    return BatchTrainResult(
-        theta=theta, series={"objective": values, "theta": thetas},
-        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
-        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
-        info=info, steps_done=steps)
+    ctx.call(path.train, *f.lead, itr, lr, *((lr_z,) if path.fitc else ()), ptr(Xt), ptr(yt), nt,
+             GPS_BATCH_STALE_NOISE if stale_noise else 0, *((ptr(draws), sets) if es else ()),
+             ptr(theta), *((ptr(Z),) if path.fitc else ()), ptr(values), ptr(thetas), ptr(obj),
+             ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
+    res = dict(theta=theta, series={"objective": values, "theta": thetas},
+               objectives=_objectives(obj), mu=mu, var=var,
+               scores=None if sc is None else {k: sc[:, q].copy()
+                                               for q, k in enumerate(SCORE_NAMES)},
+               info=info, steps_done=steps)
+    return FitcBatchTrainResult(Z=Z, **res) if path.fitc else BatchTrainResult(**res)
+
+
+def value_and_grad_batch(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
+    """Objective value and analytic gradient of B small full GPs at their own θ (one
+    gps_full_grad_batch call; per problem what GP.value_and_grad returns).  Returns
+    (values (B,), grads (B, 2 + n_ell), objectives {name: (B,)}, info (B,))."""
+    return _grad(_FULL, X, y, None, theta, objective, rbf=rbf, ctx=ctx)
 
 
 def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
@@ -208,8 +359,8 @@ def train_batch(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt
     predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score bundle against ``yt`` (B, nt).
     ``stale_noise``: the final pass uses the noise variance of the last step's forward (θ0's
     with itr = 0), the scripts' module-global sigma_noise_sq (experiment.run_method)."""
-    return _full_train("gps_full_train_batch", BATCH_MAX_N, X, y, theta0, objective, lr, itr, Xt,
-                       yt, rbf, stale_noise, ctx)
+    return _train(_FULL, X, y, None, theta0, objective, lr=lr, itr=itr, Xt=Xt, yt=yt, rbf=rbf,
+                  stale_noise=stale_noise, ctx=ctx)
 
 
 def value_and_grad_tall(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
@@ -217,8 +368,7 @@ def value_and_grad_tall(X, y, theta, objective="loo_crps", rbf=False, ctx=None):
     call, DESIGN §24: one workgroup per problem with the n×n arrays in a device workspace
     instead of LDS and the O(n³) work on the FP64 matrix instruction).  Same arguments, returns,
     refusals and ``info``; for n <= 128 the small-batch call is the faster route."""
-    return _full_value_and_grad("gps_full_grad_tall", BATCH_FULL_TALL_MAX_N, X, y, theta,
-                                objective, rbf, ctx)
+    return _grad(_FULL_TALL, X, y, None, theta, objective, rbf=rbf, ctx=ctx)
 
 
 def train_tall(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=None, rbf=False,
@@ -226,28 +376,8 @@ def train_tall(X, y, theta0, objective="loo_crps", lr=1.0, itr=400, Xt=None, yt=
     """train_batch for problems of 1 <= n <= 512 training points (one gps_full_train_tall call):
     the replicate loop of "kin40k-FULL-compare.py" (n = 500, d = 8) for B problems at once.  Same
     arguments, refusals and BatchTrainResult."""
-    return _full_train("gps_full_train_tall", BATCH_FULL_TALL_MAX_N, X, y, theta0, objective, lr,
-                       itr, Xt, yt, rbf, stale_noise, ctx)
-
-
-BLOCK_BATCH_OBJS = ["dss", "kc"]  # GPS_BLOCK_DSS, GPS_BLOCK_KC
-BATCH_BLOCK_MAX_FOLDS = 32        # GPS_BATCH_BLOCK_MAX_FOLDS
-
-
-def _block_objective(objective):
-    if objective not in BLOCK_BATCH_OBJS:
-        raise ValueError(f"objective must be one of {BLOCK_BATCH_OBJS} (the pointwise objectives go "
-                         f"through train_tall, the energy score through GP.block_loo), got "
-                         f"{objective!r}")
-    return BLOCK_BATCH_OBJS.index(objective)
-
-
-def _nfold(nfold, n):
-    hi = min(n, BATCH_BLOCK_MAX_FOLDS)
-    if isinstance(nfold, bool) or int(nfold) != nfold or not 2 <= nfold <= hi:
-        raise ValueError(f"nfold = {nfold!r}: a batched block-LOO problem of n = {n} rows has "
-                         f"2..{hi} folds")
-    return int(nfold)
+    return _train(_FULL_TALL, X, y, None, theta0, objective, lr=lr, itr=itr, Xt=Xt, yt=yt, rbf=rbf,
+                  stale_noise=stale_noise, ctx=ctx)
 
 
 def blockloo_value_and_grad_tall(X, y, theta, objective="dss", nfold=4, rbf=False, ctx=None):
@@ -257,19 +387,7 @@ def blockloo_value_and_grad_tall(X, y, theta, objective="dss", nfold=4, rbf=Fals
     Arguments, refusals and ``info`` as value_and_grad_tall; ``info`` n + k reports an internal
     error at global row k of its fold's block.  Returns (values (B,), grads (B, 2 + n_ell),
     fold_values (B, nfold), objectives {name: (B,)}, info (B,))."""
-    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
-    B, n, d = X.shape
-    th, n_ell = _thetas(theta, B, d)
-    code = _block_objective(objective)
-    nfold = _nfold(nfold, n)
-    ctx = ctx or _lib.default_context()
-    vals, fold = np.empty(B), np.empty((B, nfold))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    grad = np.empty((B, 2 + n_ell))
-    info = np.zeros(B, np.int32)
-    ctx.call("gps_full_blockloo_grad_tall", GPS_RBF if rbf else GPS_ARD, code, nfold, B, ptr(X),
-             ptr(y), n, d, ptr(th), n_ell, ptr(vals), ptr(fold), ptr(obj), ptr(grad), _iptr(info))
-    return vals, grad, fold, {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, info
+    return _grad(_FULL_BLOCK, X, y, None, theta, objective, nfold, rbf=rbf, ctx=ctx)
 
 
 def blockloo_train_tall(X, y, theta0, objective="dss", nfold=4, lr=1e-3, itr=150, Xt=None, yt=None,
@@ -279,69 +397,8 @@ def blockloo_train_tall(X, y, theta0, objective="dss", nfold=4, lr=1e-3, itr=150
     CRPS sibling "kc" (K20:655-720) for B problems at once.  ``series["objective"]`` is the block
     objective before each step; everything else as train_tall: arguments, refusals and
     BatchTrainResult."""
-    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
-    B, n, d = X.shape
-    th0, n_ell = _thetas(theta0, B, d)
-    code = _block_objective(objective)
-    nfold = _nfold(nfold, n)
-    itr, lr = _steps(itr, lr)
-    Xt, yt, nt = _tests(Xt, yt, B, d)
-    ctx = ctx or _lib.default_context()
-    nth = 2 + n_ell
-    theta = np.empty((B, nth))
-    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    mu = np.empty((B, nt)) if nt else None
-    var = np.empty((B, nt)) if nt else None
-    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
-    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call("gps_full_blockloo_train_tall", GPS_RBF if rbf else GPS_ARD, code, nfold, B, ptr(X),
-             ptr(y), n, d, ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
-             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(values), ptr(thetas),
-             ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
-    return BatchTrainResult(
-        theta=theta, series={"objective": values, "theta": thetas},
-        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
-        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
-        info=info, steps_done=steps)
-
-
-BATCH_ES_MAX_FOLD = 128  # GPS_BATCH_ES_MAX_FOLD: rows of the largest fold
-BATCH_ES_MAX_SIM = 512   # GPS_BATCH_ES_MAX_SIM
-
-
-def _es_args(nfold, n, num_sim, beta):
-    nfold = _nfold(nfold, n)
-    if -(-n // nfold) > BATCH_ES_MAX_FOLD:
-        raise ValueError(f"n = {n} rows in {nfold} folds: a batched energy-score fold holds at most "
-                         f"{BATCH_ES_MAX_FOLD} rows (its square-root work has to fit one launch), "
-                         f"use more folds")
-    if isinstance(num_sim, bool) or int(num_sim) != num_sim or not 2 <= num_sim <= BATCH_ES_MAX_SIM:
-        raise ValueError(f"num_sim = {num_sim!r}: a batched energy score takes 2..{BATCH_ES_MAX_SIM} "
-                         f"draws a fold")
-    beta = float(beta)
-    if not 0.0 < beta <= 2.0:
-        raise ValueError(f"beta must be in (0, 2], got {beta!r}")
-    return nfold, int(num_sim), beta
-
-
-def _es_draws(draws, B, sets, n, nfold, num_sim, rng):
-    """(B, sets, 2·num_sim·n) draws: the caller's, or es_draws from rng problem-major then
-    set-major."""
-    from .gp import es_draws
-    per = 2 * num_sim * n
-    if draws is None:
-        rng = np.random.default_rng(rng)
-        return np.stack([np.stack([es_draws(n, nfold, num_sim, rng) for _ in range(sets)])
-                         for _ in range(B)])
-    try:
-        draws = f64(draws)
-    except (ValueError, TypeError) as e:
-        raise ValueError(f"draws must be a rectangular array: {e}") from None
-    if draws.size != B * sets * per:
-        raise ValueError(f"draws must hold B·draw_sets·2·num_sim·n = {B}·{sets}·{per} values "
-                         f"(es_draws' layout per set), got {draws.size}")
-    return np.ascontiguousarray(draws).reshape(B, sets, per)
+    return _train(_FULL_BLOCK, X, y, None, theta0, objective, nfold, lr=lr, itr=itr, Xt=Xt, yt=yt,
+                  rbf=rbf, stale_noise=stale_noise, ctx=ctx)
 
 
 def es_value_and_grad_tall(X, y, theta, nfold=4, num_sim=300, beta=1.0, draws=None, rng=None,
@@ -355,20 +412,8 @@ def es_value_and_grad_tall(X, y, theta, nfold=4, num_sim=300, beta=1.0, draws=No
     there, 2n + 1 + f: fold f's square root would need more than 40 Newton–Schulz steps.
     Returns (values (B,), grads (B, 2 + n_ell), fold_values (B, nfold), objectives {name: (B,)},
     info (B,))."""
-    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
-    B, n, d = X.shape
-    th, n_ell = _thetas(theta, B, d)
-    nfold, num_sim, beta = _es_args(nfold, n, num_sim, beta)
-    draws = _es_draws(draws, B, 1, n, nfold, num_sim, rng)
-    ctx = ctx or _lib.default_context()
-    vals, fold = np.empty(B), np.empty((B, nfold))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    grad = np.empty((B, 2 + n_ell))
-    info = np.zeros(B, np.int32)
-    ctx.call("gps_full_es_grad_tall", GPS_RBF if rbf else GPS_ARD, nfold, num_sim, beta, B, ptr(X),
-             ptr(y), n, d, ptr(th), n_ell, ptr(draws), ptr(vals), ptr(fold), ptr(obj), ptr(grad),
-             _iptr(info))
-    return vals, grad, fold, {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, info
+    return _grad(_FULL_ES, X, y, None, theta, None, nfold, num_sim, beta, draws=draws, rng=rng,
+                 rbf=rbf, ctx=ctx)
 
 
 def es_train_tall(X, y, theta0, nfold=4, num_sim=300, beta=1.0, lr=0.1, itr=25, draws=None,
@@ -384,117 +429,16 @@ def es_train_tall(X, y, theta0, nfold=4, num_sim=300, beta=1.0, lr=0.1, itr=25, 
     ``draw_sets`` is the way out.  ``series["objective"]`` is the energy score before each step;
     limits as es_value_and_grad_tall, everything else as train_tall: arguments, refusals and
     BatchTrainResult."""
-    X, y = _problems(X, y, BATCH_FULL_TALL_MAX_N)
-    B, n, d = X.shape
-    th0, n_ell = _thetas(theta0, B, d)
-    nfold, num_sim, beta = _es_args(nfold, n, num_sim, beta)
-    itr, lr = _steps(itr, lr)
-    sets = max(itr, 1) if draw_sets is None else draw_sets
-    if isinstance(sets, bool) or int(sets) != sets or not 1 <= sets <= max(itr, 1):
-        raise ValueError(f"draw_sets = {draw_sets!r}: a fit of {itr} steps takes 1..{max(itr, 1)} "
-                         f"draw sets")
-    sets = int(sets)
-    Xt, yt, nt = _tests(Xt, yt, B, d)
-    draws = _es_draws(draws, B, sets, n, nfold, num_sim, rng)
-    ctx = ctx or _lib.default_context()
-    nth = 2 + n_ell
-    theta = np.empty((B, nth))
-    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    mu = np.empty((B, nt)) if nt else None
-    var = np.empty((B, nt)) if nt else None
-    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
-    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call("gps_full_es_train_tall", GPS_RBF if rbf else GPS_ARD, nfold, num_sim, beta, B, ptr(X),
-             ptr(y), n, d, ptr(th0), n_ell, itr, lr, ptr(Xt), ptr(yt), nt,
-             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(draws), sets, ptr(theta), ptr(values),
-             ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
-    return BatchTrainResult(
-        theta=theta, series={"objective": values, "theta": thetas},
-        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
-        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
-        info=info, steps_done=steps)
-
-
-def _inducing(Z, B, d):
-    """Z (B, m, d) checked against the batch and the kernel's limit."""
-    try:
-        Z = f64(Z)
-    except (ValueError, TypeError) as e:  # a ragged list of inducing sets
-        raise ValueError(f"Z must be a rectangular array, one m per batch: {e}") from None
-    if Z.ndim == 2 and d == 1:
-        Z = Z[:, :, None]
-    if Z.ndim != 3 or Z.shape[0] != B or Z.shape[2] != d:
-        raise ValueError(f"Z must be (B, m, d) = ({B}, m, {d}) (or (B, m) when d = 1), got {Z.shape}")
-    m = Z.shape[1]
-    if not 1 <= m <= BATCH_FITC_MAX_M:
-        raise ValueError(f"m = {m}: a batched FITC problem holds 1..{BATCH_FITC_MAX_M} inducing "
-                         f"inputs")
-    return np.ascontiguousarray(Z), m
-
-
-def _fitc_value_and_grad(entry, max_n, X, y, Z, theta, objective, ctx):
-    X, y = _problems(X, y, max_n)
-    B, n, d = X.shape
-    Z, m = _inducing(Z, B, d)
-    th, n_ell = _thetas(theta, B, d)
-    code = _objective(objective)
-    ctx = ctx or _lib.default_context()
-    obj = np.empty((B, len(OBJ_NAMES)))
-    grad = np.empty((B, 2 + n_ell))
-    gz = np.empty((B, m, d))
-    info = np.zeros(B, np.int32)
-    ctx.call(entry, code, B, ptr(X), ptr(y), n, d, ptr(Z), m, ptr(th), n_ell,
-             ptr(obj), ptr(grad), ptr(gz), _iptr(info))
-    objs = {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}
-    return objs[objective], grad, gz, objs, info
+    return _train(_FULL_ES, X, y, None, theta0, None, nfold, num_sim, beta, lr=lr, itr=itr,
+                  draws=draws, draw_sets=draw_sets, rng=rng, Xt=Xt, yt=yt, rbf=rbf,
+                  stale_noise=stale_noise, ctx=ctx)
 
 
 def fitc_value_and_grad_batch(X, y, Z, theta, objective="loo_crps", ctx=None):
     """Objective value and analytic gradient of B small FITC GPs at their own (θ, Z) (one
     gps_fitc_grad_batch call; per problem what GP.value_and_grad(..., Z=Z) returns).  Returns
     (values (B,), grads (B, 2 + n_ell), grad_Z (B, m, d), objectives {name: (B,)}, info (B,))."""
-    return _fitc_value_and_grad("gps_fitc_grad_batch", BATCH_MAX_N, X, y, Z, theta, objective,
-                                ctx)
-
-
-@dataclass
-class FitcBatchTrainResult(BatchTrainResult):
-    """fitc_train_batch's outputs: BatchTrainResult's fields and ``Z`` (B, m, d), the final
-    inducing inputs.  ``info`` is 0, k in 1..m (K(Z,Z) + 1e-3·I's leading minor) or m + k (B's)."""
-    Z: np.ndarray = None
-
-
-def _fitc_train(entry, max_n, X, y, Z0, theta0, objective, lr, lr_z, itr, Xt, yt, stale_noise,
-                ctx):
-    X, y = _problems(X, y, max_n)
-    B, n, d = X.shape
-    Z0, m = _inducing(Z0, B, d)
-    th0, n_ell = _thetas(theta0, B, d)
-    code = _objective(objective)
-    itr, lr = _steps(itr, lr)
-    lr_z = lr if lr_z is None else float(lr_z)
-    if not np.isfinite(lr_z):
-        raise ValueError(f"lr_z must be finite, got {lr_z!r}")
-    Xt, yt, nt = _tests(Xt, yt, B, d)
-    ctx = ctx or _lib.default_context()
-    nth = 2 + n_ell
-    theta, Z = np.empty((B, nth)), np.empty((B, m, d))
-    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    mu = np.empty((B, nt)) if nt else None
-    var = np.empty((B, nt)) if nt else None
-    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
-    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call(entry, code, B, ptr(X), ptr(y), n, d, ptr(Z0), m, ptr(th0), n_ell,
-             itr, lr, lr_z, ptr(Xt), ptr(yt), nt, GPS_BATCH_STALE_NOISE if stale_noise else 0,
-             ptr(theta), ptr(Z), ptr(values), ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc),
-             _iptr(info), _iptr(steps))
-    return FitcBatchTrainResult(
-        theta=theta, series={"objective": values, "theta": thetas},
-        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
-        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
-        info=info, steps_done=steps, Z=Z)
+    return _grad(_FITC, X, y, Z, theta, objective, ctx=ctx)
 
 
 def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, itr=400, Xt=None,
@@ -503,8 +447,8 @@ def fitc_train_batch(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, 
     SF:229-233; lr_z defaults to lr) for B small FITC GPs at once on the device, then one forward
     at the final θ and Z with the test predictive at ``Xt`` ((B, nt, d) or (B, nt)) and its score
     bundle against ``yt`` (B, nt).  ``stale_noise`` as train_batch."""
-    return _fitc_train("gps_fitc_train_batch", BATCH_MAX_N, X, y, Z0, theta0, objective, lr, lr_z,
-                       itr, Xt, yt, stale_noise, ctx)
+    return _train(_FITC, X, y, Z0, theta0, objective, lr=lr, lr_z=lr_z, itr=itr, Xt=Xt, yt=yt,
+                  stale_noise=stale_noise, ctx=ctx)
 
 
 def fitc_value_and_grad_tall(X, y, Z, theta, objective="loo_crps", ctx=None):
@@ -512,8 +456,7 @@ def fitc_value_and_grad_tall(X, y, Z, theta, objective="loo_crps", ctx=None):
     DESIGN §22: one workgroup per problem with the n-sized arrays in a device workspace instead
     of LDS).  Same arguments, returns, refusals and ``info``; for n <= 128 the small-batch call
     is the faster route."""
-    return _fitc_value_and_grad("gps_fitc_grad_tall", BATCH_FITC_TALL_MAX_N, X, y, Z, theta,
-                                objective, ctx)
+    return _grad(_FITC_TALL, X, y, Z, theta, objective, ctx=ctx)
 
 
 def fitc_train_tall(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, itr=400, Xt=None,
@@ -521,8 +464,8 @@ def fitc_train_tall(X, y, Z0, theta0, objective="loo_crps", lr=1.0, lr_z=None, i
     """fitc_train_batch for tall problems, 1 <= n <= 2048 (one gps_fitc_train_tall call): the
     replicate loops of "KIN40K-COMPARE-ALL-FITC-20" (n = 500, d = 8, m = 20) for B problems at
     once.  Same arguments, refusals and FitcBatchTrainResult."""
-    return _fitc_train("gps_fitc_train_tall", BATCH_FITC_TALL_MAX_N, X, y, Z0, theta0, objective,
-                       lr, lr_z, itr, Xt, yt, stale_noise, ctx)
+    return _train(_FITC_TALL, X, y, Z0, theta0, objective, lr=lr, lr_z=lr_z, itr=itr, Xt=Xt, yt=yt,
+                  stale_noise=stale_noise, ctx=ctx)
 
 
 def fitc_blockloo_value_and_grad_tall(X, y, Z, theta, objective="dss", nfold=4, ctx=None):
@@ -532,21 +475,7 @@ def fitc_blockloo_value_and_grad_tall(X, y, Z, theta, objective="dss", nfold=4, 
     Arguments, refusals and ``info`` as fitc_value_and_grad_tall; ``info`` (2 + f)·m + k reports an
     internal error in fold f's factorisation.  Returns (values (B,), grads (B, 2 + n_ell), grad_Z
     (B, m, d), fold_values (B, nfold), objectives {name: (B,)}, info (B,))."""
-    X, y = _problems(X, y, BATCH_FITC_TALL_MAX_N)
-    B, n, d = X.shape
-    Z, m = _inducing(Z, B, d)
-    th, n_ell = _thetas(theta, B, d)
-    code = _block_objective(objective)
-    nfold = _nfold(nfold, n)
-    ctx = ctx or _lib.default_context()
-    vals, fold = np.empty(B), np.empty((B, nfold))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    grad = np.empty((B, 2 + n_ell))
-    gz = np.empty((B, m, d))
-    info = np.zeros(B, np.int32)
-    ctx.call("gps_fitc_blockloo_grad_tall", code, nfold, B, ptr(X), ptr(y), n, d, ptr(Z), m,
-             ptr(th), n_ell, ptr(vals), ptr(fold), ptr(obj), ptr(grad), ptr(gz), _iptr(info))
-    return vals, grad, gz, fold, {k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, info
+    return _grad(_FITC_BLOCK, X, y, Z, theta, objective, nfold, ctx=ctx)
 
 
 def fitc_blockloo_train_tall(X, y, Z0, theta0, objective="dss", nfold=4, lr=1e-3, lr_z=None,
@@ -556,32 +485,5 @@ def fitc_blockloo_train_tall(X, y, Z0, theta0, objective="dss", nfold=4, lr=1e-3
     defaults here) or its CRPS sibling "kc" (K20:655-726, lr = lr_z = 0.1) for B problems at once.
     ``series["objective"]`` is the block objective before each step; everything else as
     fitc_train_tall: arguments, refusals and FitcBatchTrainResult."""
-    X, y = _problems(X, y, BATCH_FITC_TALL_MAX_N)
-    B, n, d = X.shape
-    Z0, m = _inducing(Z0, B, d)
-    th0, n_ell = _thetas(theta0, B, d)
-    code = _block_objective(objective)
-    nfold = _nfold(nfold, n)
-    itr, lr = _steps(itr, lr)
-    lr_z = lr if lr_z is None else float(lr_z)
-    if not np.isfinite(lr_z):
-        raise ValueError(f"lr_z must be finite, got {lr_z!r}")
-    Xt, yt, nt = _tests(Xt, yt, B, d)
-    ctx = ctx or _lib.default_context()
-    nth = 2 + n_ell
-    theta, Z = np.empty((B, nth)), np.empty((B, m, d))
-    values, thetas = np.empty((B, itr)), np.empty((B, itr, nth))
-    obj = np.empty((B, len(OBJ_NAMES)))
-    mu = np.empty((B, nt)) if nt else None
-    var = np.empty((B, nt)) if nt else None
-    sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
-    info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call("gps_fitc_blockloo_train_tall", code, nfold, B, ptr(X), ptr(y), n, d, ptr(Z0), m,
-             ptr(th0), n_ell, itr, lr, lr_z, ptr(Xt), ptr(yt), nt,
-             GPS_BATCH_STALE_NOISE if stale_noise else 0, ptr(theta), ptr(Z), ptr(values),
-             ptr(thetas), ptr(obj), ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
-    return FitcBatchTrainResult(
-        theta=theta, series={"objective": values, "theta": thetas},
-        objectives={k: obj[:, q].copy() for q, k in enumerate(OBJ_NAMES)}, mu=mu, var=var,
-        scores=None if sc is None else {k: sc[:, q].copy() for q, k in enumerate(SCORE_NAMES)},
-        info=info, steps_done=steps, Z=Z)
+    return _train(_FITC_BLOCK, X, y, Z0, theta0, objective, nfold, lr=lr, lr_z=lr_z, itr=itr, Xt=Xt,
+                  yt=yt, stale_noise=stale_noise, ctx=ctx)

@@ -36,8 +36,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import NotPositiveDefinite
-from .batch import (BLOCK_BATCH_OBJS, blockloo_train_tall, es_train_tall, fitc_blockloo_train_tall,
-                    fitc_train_batch, fitc_train_tall, train_batch, train_tall)
+from .batch import (BATCH_OBJS, BLOCK_BATCH_OBJS, blockloo_train_tall, es_train_tall,
+                    fitc_blockloo_train_tall, fitc_train_batch, fitc_train_tall, train_batch,
+                    train_tall)
 from .gp import GP
 
 SHEETS = ("trainx", "trainy", "testx", "testy")
@@ -311,7 +312,73 @@ def run_simple_fitc(TT=100, methods=None, datasets=None, Z0=None, itr=None, stal
     return out
 
 
-BATCH_OBJECTIVES = ("nlml", "loo_crps", "loo_logs")  # what the batched FITC kernels can fit
+BATCH_OBJECTIVES = BATCH_OBJS  # what the batched pointwise kernels can fit
+
+
+def _run_batch(who, sheets, TT, methods, accepts, why, route, train, what, m=None, es=None,
+               zero_for=(), itr=None, seed=None, reseed=True, stale_noise=True, ctx=None):
+    """The replicate runner behind the run_*_batch functions (``who``: the caller's name in its
+    messages).  Every method's objective must be in ``accepts``, else ValueError "<why>; use
+    <route(objective)> for it".  Data replicates and starting points are drawn as run draws them:
+    replicate-major, then method by method initial_theta, then Z0 (m given: FITC, U(0,1) or N(0,1)
+    by the method's z_init) or one es_draws set per step (es = (nfold, num_sim)).  Then one call a
+    method, ``train(X, y, th0, Z0 or draws or None, method, lr=, itr=, Xt=, yt=, stale_noise=,
+    ctx=)``.  A failed replicate of a method whose objective is in ``zero_for`` gets zero metrics
+    (run_method's rule); of any other raises NotPositiveDefinite "...: <what> after k steps".
+    Returns {method: {metric: array(TT), "theta"[, "Z" with m][, "failed" with zero_for]}}."""
+    from .gp import es_draws
+    for name, meth in methods.items():
+        if meth.objective not in accepts:
+            raise ValueError(f"{who}: method {name!r} has objective {meth.objective!r}, {why}; use "
+                             f"{route(meth.objective)} for it")
+    if int(TT) != TT or TT < 1:
+        raise ValueError(f"TT must be a positive integer, got {TT!r}")
+    if m is not None and (int(m) != m or m < 1):
+        raise ValueError(f"m must be a positive integer, got {m!r}")
+    TT = int(TT)
+    rng = np.random.default_rng(seed)
+    rs = None if reseed else random.Random()
+    n_pool = sheets["trainx"].shape[0]
+    steps = {name: meth.itr if itr is None else int(itr) for name, meth in methods.items()}
+    data, th0, start = [], {name: [] for name in methods}, {name: [] for name in methods}
+    for j in range(TT):
+        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
+        data.append(dd)
+        n, d = dd["train_x"].shape
+        for name, meth in methods.items():
+            k, ell, noise = initial_theta(meth, d, rng)
+            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
+            if m is not None:
+                start[name].append(rng.random((int(m), d)) if meth.z_init == "rand"
+                                   else rng.standard_normal((int(m), d)))
+            elif es is not None:
+                start[name].append(np.stack([es_draws(n, *es, rng)
+                                             for _ in range(max(steps[name], 1))]))
+    X = np.stack([dd["train_x"] for dd in data])
+    y = np.stack([dd["train_y"] for dd in data])
+    Xt = np.stack([dd["test_x"] for dd in data])
+    yt = np.stack([dd["test_y"] for dd in data])
+    out = {}
+    for name, meth in methods.items():
+        res = train(X, y, np.stack(th0[name]), np.stack(start[name]) if start[name] else None,
+                    meth, lr=meth.lr, itr=steps[name], Xt=Xt, yt=yt, stale_noise=stale_noise,
+                    ctx=ctx)
+        failed = np.asarray(res.info) != 0
+        if failed.any() and meth.objective not in zero_for:
+            q = int(np.flatnonzero(failed)[0])
+            raise NotPositiveDefinite(int(res.info[q]), f"{who}: method {name!r}, replicate {q}: "
+                                      + what.format(info=int(res.info[q]))
+                                      + f" after {int(res.steps_done[q])} steps")
+        out[name] = {k: np.where(failed, 0.0, res.scores["test_" + k]) for k in METRICS}
+        if m is not None:
+            out[name]["Z"] = res.Z.copy()
+        out[name]["theta"] = res.theta.copy()
+        if zero_for:
+            out[name]["failed"] = failed
+    return out
+
+
+_FITC_INFO = "info = {info} (k: the leading minor of order k of K(Z,Z) + 1e-3 I, m + k: of B"
 
 
 def run_fitc_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=None, reseed=True,
@@ -329,50 +396,12 @@ def run_fitc_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=None, resee
     raises NotPositiveDefinite."""
     if methods is None:
         methods = {k: K20_METHODS[k] for k in ("crps", "nlml", "logs")}
-    for name, meth in methods.items():
-        if meth.objective not in BATCH_OBJECTIVES:
-            raise ValueError(f"run_fitc_batch: method {name!r} has objective {meth.objective!r}, "
-                             f"which has no batched path (only {BATCH_OBJECTIVES}); use "
-                             f"run(kind=\"fitc\") for it")
-    if int(TT) != TT or TT < 1:
-        raise ValueError(f"TT must be a positive integer, got {TT!r}")
-    if int(m) != m or m < 1:
-        raise ValueError(f"m must be a positive integer, got {m!r}")
-    TT, m = int(TT), int(m)
-    rng = np.random.default_rng(seed)
-    rs = None if reseed else random.Random()
-    n_pool = sheets["trainx"].shape[0]
-    data, th0, Z0 = [], {name: [] for name in methods}, {name: [] for name in methods}
-    for j in range(TT):
-        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
-        data.append(dd)
-        d = dd["train_x"].shape[1]
-        for name, meth in methods.items():
-            k, ell, noise = initial_theta(meth, d, rng)
-            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
-            Z0[name].append(rng.random((m, d)) if meth.z_init == "rand"
-                            else rng.standard_normal((m, d)))
-    X = np.stack([dd["train_x"] for dd in data])
-    y = np.stack([dd["train_y"] for dd in data])
-    Xt = np.stack([dd["test_x"] for dd in data])
-    yt = np.stack([dd["test_y"] for dd in data])
-    out = {}
-    for name, meth in methods.items():
-        res = fitc_train_tall(X, y, np.stack(Z0[name]), np.stack(th0[name]), meth.objective,
-                              lr=meth.lr, lr_z=meth.lr_z,
-                              itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
-                              stale_noise=stale_noise, ctx=ctx)
-        bad = np.flatnonzero(res.info)
-        if bad.size:
-            q = int(bad[0])
-            raise NotPositiveDefinite(int(res.info[q]), f"run_fitc_batch: method {name!r}, "
-                                      f"replicate {q}: info = {int(res.info[q])} (k: the leading "
-                                      f"minor of order k of K(Z,Z) + 1e-3 I, m + k: of B) after "
-                                      f"{int(res.steps_done[q])} steps")
-        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
-        out[name]["Z"] = res.Z.copy()
-        out[name]["theta"] = res.theta.copy()
-    return out
+    return _run_batch(
+        "run_fitc_batch", sheets, TT, methods, BATCH_OBJECTIVES,
+        f"which has no batched path (only {BATCH_OBJECTIVES})", lambda o: "run(kind=\"fitc\")",
+        lambda X, y, th0, Z0, meth, **kw: fitc_train_tall(X, y, Z0, th0, meth.objective,
+                                                          lr_z=meth.lr_z, **kw),
+        _FITC_INFO + ")", m=m, itr=itr, seed=seed, reseed=reseed, stale_noise=stale_noise, ctx=ctx)
 
 
 def run_full_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
@@ -390,44 +419,12 @@ def run_full_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True
     raises NotPositiveDefinite."""
     if methods is None:
         methods = {k: KF_METHODS[k] for k in ("crps", "nlml", "logs")}
-    for name, meth in methods.items():
-        if meth.objective not in BATCH_OBJECTIVES:
-            raise ValueError(f"run_full_batch: method {name!r} has objective {meth.objective!r}, "
-                             f"which has no batched path (only {BATCH_OBJECTIVES}); use "
-                             f"run(kind=\"full\") for it")
-    if int(TT) != TT or TT < 1:
-        raise ValueError(f"TT must be a positive integer, got {TT!r}")
-    TT = int(TT)
-    rng = np.random.default_rng(seed)
-    rs = None if reseed else random.Random()
-    n_pool = sheets["trainx"].shape[0]
-    data, th0 = [], {name: [] for name in methods}
-    for j in range(TT):
-        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
-        data.append(dd)
-        d = dd["train_x"].shape[1]
-        for name, meth in methods.items():
-            k, ell, noise = initial_theta(meth, d, rng)
-            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
-    X = np.stack([dd["train_x"] for dd in data])
-    y = np.stack([dd["train_y"] for dd in data])
-    Xt = np.stack([dd["test_x"] for dd in data])
-    yt = np.stack([dd["test_y"] for dd in data])
-    out = {}
-    for name, meth in methods.items():
-        res = train_tall(X, y, np.stack(th0[name]), meth.objective, lr=meth.lr,
-                         itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
-                         stale_noise=stale_noise, ctx=ctx)
-        bad = np.flatnonzero(res.info)
-        if bad.size:
-            q = int(bad[0])
-            raise NotPositiveDefinite(int(res.info[q]), f"run_full_batch: method {name!r}, "
-                                      f"replicate {q}: the leading minor of order "
-                                      f"{int(res.info[q])} is not positive definite after "
-                                      f"{int(res.steps_done[q])} steps")
-        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
-        out[name]["theta"] = res.theta.copy()
-    return out
+    return _run_batch(
+        "run_full_batch", sheets, TT, methods, BATCH_OBJECTIVES,
+        f"which has no batched path (only {BATCH_OBJECTIVES})", lambda o: "run(kind=\"full\")",
+        lambda X, y, th0, _, meth, **kw: train_tall(X, y, th0, meth.objective, **kw),
+        "the leading minor of order {info} is not positive definite", itr=itr, seed=seed,
+        reseed=reseed, stale_noise=stale_noise, ctx=ctx)
 
 
 def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
@@ -445,44 +442,14 @@ def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, re
     NotPositiveDefinite."""
     if methods is None:
         methods = {"dss": KF_METHODS["dss"]}
-    for name, meth in methods.items():
-        if meth.objective not in BLOCK_BATCH_OBJS:
-            route = "run(kind=\"full\")" if meth.objective == "es" else "run_full_batch"
-            raise ValueError(f"run_full_blockloo_batch: method {name!r} has objective "
-                             f"{meth.objective!r}, not one of {BLOCK_BATCH_OBJS}; use {route} for it")
-    if int(TT) != TT or TT < 1:
-        raise ValueError(f"TT must be a positive integer, got {TT!r}")
-    TT = int(TT)
-    rng = np.random.default_rng(seed)
-    rs = None if reseed else random.Random()
-    n_pool = sheets["trainx"].shape[0]
-    data, th0 = [], {name: [] for name in methods}
-    for j in range(TT):
-        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
-        data.append(dd)
-        d = dd["train_x"].shape[1]
-        for name, meth in methods.items():
-            k, ell, noise = initial_theta(meth, d, rng)
-            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
-    X = np.stack([dd["train_x"] for dd in data])
-    y = np.stack([dd["train_y"] for dd in data])
-    Xt = np.stack([dd["test_x"] for dd in data])
-    yt = np.stack([dd["test_y"] for dd in data])
-    out = {}
-    for name, meth in methods.items():
-        res = blockloo_train_tall(X, y, np.stack(th0[name]), meth.objective, nfold=nfold,
-                                  lr=meth.lr, itr=meth.itr if itr is None else int(itr), Xt=Xt,
-                                  yt=yt, stale_noise=stale_noise, ctx=ctx)
-        bad = np.flatnonzero(res.info)
-        if bad.size:
-            q = int(bad[0])
-            raise NotPositiveDefinite(int(res.info[q]), f"run_full_blockloo_batch: method {name!r}, "
-                                      f"replicate {q}: info {int(res.info[q])} (the failing "
-                                      f"leading minor, or n + the fold block's row) after "
-                                      f"{int(res.steps_done[q])} steps")
-        out[name] = {k: res.scores["test_" + k].copy() for k in METRICS}
-        out[name]["theta"] = res.theta.copy()
-    return out
+    return _run_batch(
+        "run_full_blockloo_batch", sheets, TT, methods, BLOCK_BATCH_OBJS,
+        f"not one of {BLOCK_BATCH_OBJS}",
+        lambda o: "run(kind=\"full\")" if o == "es" else "run_full_batch",
+        lambda X, y, th0, _, meth, **kw: blockloo_train_tall(X, y, th0, meth.objective,
+                                                             nfold=nfold, **kw),
+        "info {info} (the failing leading minor, or n + the fold block's row)", itr=itr, seed=seed,
+        reseed=reseed, stale_noise=stale_noise, ctx=ctx)
 
 
 def run_full_es_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
@@ -498,46 +465,15 @@ def run_full_es_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=T
     method subset run(kind="full", methods=subset) and this fit the same problems with the same
     draws.  ``itr`` overrides the methods' step counts; stale_noise as run_method.  A replicate
     whose factorisation fails gets zero metrics as in run_method (KF:726-732)."""
-    from .gp import es_draws
     if methods is None:
         methods = {"es": KF_METHODS["es"]}
-    for name, meth in methods.items():
-        if meth.objective != "es":
-            route = "run_full_blockloo_batch" if meth.objective in BLOCK_BATCH_OBJS else "run_full_batch"
-            raise ValueError(f"run_full_es_batch: method {name!r} has objective {meth.objective!r}, "
-                             f"not 'es'; use {route} for it")
-    if int(TT) != TT or TT < 1:
-        raise ValueError(f"TT must be a positive integer, got {TT!r}")
-    TT = int(TT)
-    rng = np.random.default_rng(seed)
-    rs = None if reseed else random.Random()
-    n_pool = sheets["trainx"].shape[0]
-    steps = {name: meth.itr if itr is None else int(itr) for name, meth in methods.items()}
-    data, th0, draws = [], {name: [] for name in methods}, {name: [] for name in methods}
-    for j in range(TT):
-        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
-        data.append(dd)
-        n, d = dd["train_x"].shape
-        for name, meth in methods.items():
-            k, ell, noise = initial_theta(meth, d, rng)
-            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
-            draws[name].append(np.stack([es_draws(n, nfold, num_sim, rng)
-                                         for _ in range(max(steps[name], 1))]))
-    X = np.stack([dd["train_x"] for dd in data])
-    y = np.stack([dd["train_y"] for dd in data])
-    Xt = np.stack([dd["test_x"] for dd in data])
-    yt = np.stack([dd["test_y"] for dd in data])
-    out = {}
-    for name, meth in methods.items():
-        res = es_train_tall(X, y, np.stack(th0[name]), nfold=nfold, num_sim=num_sim, lr=meth.lr,
-                            itr=steps[name], draws=np.stack(draws[name]),
-                            draw_sets=max(steps[name], 1), Xt=Xt, yt=yt, stale_noise=stale_noise,
-                            ctx=ctx)
-        failed = np.asarray(res.info) != 0
-        out[name] = {k: np.where(failed, 0.0, res.scores["test_" + k]) for k in METRICS}
-        out[name]["theta"] = res.theta.copy()
-        out[name]["failed"] = failed
-    return out
+    return _run_batch(
+        "run_full_es_batch", sheets, TT, methods, ("es",), "not 'es'",
+        lambda o: "run_full_blockloo_batch" if o in BLOCK_BATCH_OBJS else "run_full_batch",
+        lambda X, y, th0, draws, meth, **kw: es_train_tall(
+            X, y, th0, nfold=nfold, num_sim=num_sim, draws=draws, draw_sets=draws.shape[1], **kw),
+        "", es=(nfold, num_sim), zero_for=("es",), itr=itr, seed=seed, reseed=reseed,
+        stale_noise=stale_noise, ctx=ctx)
 
 
 def run_fitc_blockloo_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=None, reseed=True,
@@ -557,48 +493,11 @@ def run_fitc_blockloo_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=No
     dss replicate that fails raises NotPositiveDefinite."""
     if methods is None:
         methods = {k: K20_METHODS[k] for k in ("dss", "kc")}
-    for name, meth in methods.items():
-        if meth.objective not in BLOCK_BATCH_OBJS:
-            route = "run(kind=\"fitc\")" if meth.objective == "es" else "run_fitc_batch"
-            raise ValueError(f"run_fitc_blockloo_batch: method {name!r} has objective "
-                             f"{meth.objective!r}, not one of {BLOCK_BATCH_OBJS}; use {route} for it")
-    if int(TT) != TT or TT < 1:
-        raise ValueError(f"TT must be a positive integer, got {TT!r}")
-    if int(m) != m or m < 1:
-        raise ValueError(f"m must be a positive integer, got {m!r}")
-    TT, m = int(TT), int(m)
-    rng = np.random.default_rng(seed)
-    rs = None if reseed else random.Random()
-    n_pool = sheets["trainx"].shape[0]
-    data, th0, Z0 = [], {name: [] for name in methods}, {name: [] for name in methods}
-    for j in range(TT):
-        dd = replicate(sheets, j if reseed else None, n_pool=n_pool, rs=rs)
-        data.append(dd)
-        d = dd["train_x"].shape[1]
-        for name, meth in methods.items():
-            k, ell, noise = initial_theta(meth, d, rng)
-            th0[name].append(np.concatenate([[k], np.ravel(ell), [noise]]))
-            Z0[name].append(rng.random((m, d)) if meth.z_init == "rand"
-                            else rng.standard_normal((m, d)))
-    X = np.stack([dd["train_x"] for dd in data])
-    y = np.stack([dd["train_y"] for dd in data])
-    Xt = np.stack([dd["test_x"] for dd in data])
-    yt = np.stack([dd["test_y"] for dd in data])
-    out = {}
-    for name, meth in methods.items():
-        res = fitc_blockloo_train_tall(X, y, np.stack(Z0[name]), np.stack(th0[name]),
-                                       meth.objective, nfold=nfold, lr=meth.lr, lr_z=meth.lr_z,
-                                       itr=meth.itr if itr is None else int(itr), Xt=Xt, yt=yt,
-                                       stale_noise=stale_noise, ctx=ctx)
-        failed = np.asarray(res.info) != 0
-        if failed.any() and meth.objective != "kc":
-            q = int(np.flatnonzero(failed)[0])
-            raise NotPositiveDefinite(int(res.info[q]), f"run_fitc_blockloo_batch: method {name!r}, "
-                                      f"replicate {q}: info = {int(res.info[q])} (k: the leading "
-                                      f"minor of order k of K(Z,Z) + 1e-3 I, m + k: of B, (2 + f) m "
-                                      f"+ k: of fold f's B) after {int(res.steps_done[q])} steps")
-        out[name] = {k: np.where(failed, 0.0, res.scores["test_" + k]) for k in METRICS}
-        out[name]["Z"] = res.Z.copy()
-        out[name]["theta"] = res.theta.copy()
-        out[name]["failed"] = failed
-    return out
+    return _run_batch(
+        "run_fitc_blockloo_batch", sheets, TT, methods, BLOCK_BATCH_OBJS,
+        f"not one of {BLOCK_BATCH_OBJS}",
+        lambda o: "run(kind=\"fitc\")" if o == "es" else "run_fitc_batch",
+        lambda X, y, th0, Z0, meth, **kw: fitc_blockloo_train_tall(
+            X, y, Z0, th0, meth.objective, nfold=nfold, lr_z=meth.lr_z, **kw),
+        _FITC_INFO + ", (2 + f) m + k: of fold f's B)", m=m, zero_for=("kc",), itr=itr, seed=seed,
+        reseed=reseed, stale_noise=stale_noise, ctx=ctx)
