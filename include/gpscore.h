@@ -714,6 +714,41 @@ int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfol
                                  double* theta_out, double* values, double* thetas, double* obj,
                                  double* mu, double* var, double* sc, int* info, int* steps_done);
 
+/* ---- the same fits with a validation set scored step by step -----------------------
+ * gps_full_train_tall and gps_full_blockloo_train_tall with every problem's own validation rows Xv
+ * (nprob·nv·d) and targets yv (nprob·nv) scored INSIDE the fit: the per-iteration validation
+ * series the scripts carry commented out (KF:441-449, 557-563, 678-684; K20:258-264, 469-476),
+ * from the factorisation the step has in hand.  Everything up to steps_done means what it means
+ * there, and the fit itself — theta_out, values, thetas, obj, mu, var, sc, info, steps_done — is
+ * bitwise what those calls return.  Checkpoints: training step i (0-based) with i % va_every == 0
+ * writes the six GPS_SC_* scores of the predictive at Xv against yv (and the problem's own
+ * train-target mean and unbiased variance) to va_sc[(q·nva + i / va_every)·GPS_N_SC + ·], at the
+ * parameters of that step's forward: θ before step i with its own σ², the model values[q·itr + i]
+ * describes.  The final pass adds the last row, nva − 1 with nva = ceil(itr / va_every) + 1, at
+ * the final pass's parameters, so it honours GPS_BATCH_STALE_NOISE: with that flag and itr = k it
+ * is the scripts' va_series[k − 1] — the kernel parameters after update k − 1 with the σ² of
+ * forward k − 1 (KF:239 against KF:441-449); without it, the score at the final θ.  Each row is
+ * bitwise the sc of an itr = 0 call of the plain entry point at that θ with Xt = Xv, yt = yv, and
+ * is independent of nprob, position and launch split.  A failed problem keeps the rows it reached
+ * and gets NaN in every later row, the final row included.  Xv, yv and va_sc (nprob·nva·GPS_N_SC)
+ * are required; 1 <= nv <= 2^24, 1 <= va_every <= 2^20; the 8 GiB guard counts Xv, yv and va_sc.
+ * The LDS and the workspace are those of the plain calls; a checkpoint costs about n²·nv flops. */
+int gps_full_train_tall_va(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                           const double* y, int64_t n, int d, const double* theta0, int n_ell,
+                           int64_t itr, double lr, const double* Xv, const double* yv, int64_t nv,
+                           int64_t va_every, const double* Xt, const double* yt, int64_t nt,
+                           int flags, double* theta_out, double* values, double* thetas,
+                           double* obj, double* mu, double* var, double* sc, double* va_sc,
+                           int* info, int* steps_done);
+int gps_full_blockloo_train_tall_va(gps_ctx* ctx, int kind, int objective, int nfold,
+                                    int64_t nprob, const double* X, const double* y, int64_t n,
+                                    int d, const double* theta0, int n_ell, int64_t itr, double lr,
+                                    const double* Xv, const double* yv, int64_t nv,
+                                    int64_t va_every, const double* Xt, const double* yt,
+                                    int64_t nt, int flags, double* theta_out, double* values,
+                                    double* thetas, double* obj, double* mu, double* var,
+                                    double* sc, double* va_sc, int* info, int* steps_done);
+
 /* ---- batches of full GPs of up to 512 rows on the block-LOO energy score --------
  * gps_full_blockloo_es (KF:607-663) and the SGD fit around it (KF:665-732: 25 steps at lr 0.1,
  * 300 draws a fold, redrawn every step) for a whole batch: the model, limits (1 <= n <= 512, d <=

@@ -14,13 +14,13 @@
 // value + gradient of every problem at its own θ (and Z), and the SGD fit loops of the scripts'
 // replicate loops for a whole batch with the final predictive and score bundle.  The calls own
 // their device buffers:
-//   btin     X | y | Xt | yt | the energy score's draws
+//   btin     X | y | Xt | yt | the energy score's draws | Xv | yv (the gps_*_va calls)
 //   btstate  θ (nprob·nth) | stale log σ² (nprob) | Z (nprob·m·d, FITC) | the tall kernels'
 //            per-problem workspace; the full-tall path pads the head to a multiple of 8 doubles
 //            (its workspace is read in 16-byte pieces)
 //   btint    info | steps_done
 //   btout    GRAD: obj | grad | grad_z | value | fold_values (the last two: block-LOO);
-//            TRAIN: values | thetas | obj | mu | var | sc
+//            TRAIN: values | thetas | obj | mu | var | sc | va_sc
 // Every call uploads all it reads, so nothing is carried from one batch call to the next; the
 // resident full-GP / FITC data, any fit and the test buffers are not touched, and nothing is
 // sharded, so a communicator does not matter.  A path is one Path constant: its limit on n, its
@@ -104,6 +104,27 @@ const Path<BatchParams> kFullTallBlock = {
     [](gps_ctx*, const BatchParams& p, double* ws, int64_t stride, const Block& b,
        hipStream_t s) {
       return launch_batch_full_tall_block(
+          BatchFullTallBlockParams{p, ws, stride, b.nfold, 0, b.value, b.fold_values}, s);
+    },
+    true};
+// the two tall full-GP paths with a validation set scored inside the fit: training
+// calls only, the grad tags are never used
+const Path<BatchParams> kFullTallVa = {
+    GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_va_grad",
+    "batch_full_tall_va_train", [](int64_t n, int, int, int) { return batch_full_tall_ws_doubles(n); },
+    true, batch_full_tall_steps,
+    [](gps_ctx*, const BatchParams& p, double* ws, int64_t stride, const Block&, hipStream_t s) {
+      return launch_batch_full_tall_va(BatchFullTallParams{p, ws, stride}, s);
+    },
+    false};
+const Path<BatchParams> kFullTallBlockVa = {
+    GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_block_va_grad",
+    "batch_full_tall_block_va_train",
+    [](int64_t n, int, int nfold, int) { return batch_full_tall_block_ws_doubles(n, nfold); }, true,
+    batch_full_tall_steps,
+    [](gps_ctx*, const BatchParams& p, double* ws, int64_t stride, const Block& b,
+       hipStream_t s) {
+      return launch_batch_full_tall_block_va(
           BatchFullTallBlockParams{p, ws, stride, b.nfold, 0, b.value, b.fold_values}, s);
     },
     true};
@@ -196,17 +217,26 @@ int check_problem(gps_ctx* ctx, const Path<P>& path, const Problem& a) {
   return 0;
 }
 
-// Sizes the four buffers (nt test rows a problem, n_out output doubles, n_ws workspace doubles in
-// all) and fills p with the problem and the carving of btin, btstate and btint; *ws is the
+// the validation set of a gps_*_va call: rows, targets, their count a problem, the checkpoint
+// spacing and the output
+struct Va {
+  const double *Xv, *yv;
+  int64_t nv, va_every;
+  double* va_sc;
+};
+
+// Sizes the four buffers (nt test rows and nv validation rows a problem, n_out output doubles, n_ws
+// workspace doubles in all) and fills p with the problem and the carving of btin, btstate and btint; *ws is the
 // workspace behind the state's head.
 template <class P>
 int carve(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t nt, int64_t n_out,
-          int64_t n_ws, P& p, double** ws) {
+          int64_t n_ws, P& p, double** ws, int64_t nv = 0) {
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
   int64_t head = nprob * (nth + 1 + nz);
   if (path.pad) head = (head + 7) / 8 * 8;
   HIPCHK(ensure(ctx, ctx->btin,
-                (size_t)(nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + a.n_draws()) * 8));
+                (size_t)(nprob * a.n * (a.d + 1) + nprob * (nt + nv) * (a.d + 1) + a.n_draws()) *
+                    8));
   HIPCHK(ensure(ctx, ctx->btstate, (size_t)(head + n_ws) * 8));
   HIPCHK(ensure(ctx, ctx->btint, (size_t)(2 * nprob) * sizeof(int)));
   HIPCHK(ensure(ctx, ctx->btout, (size_t)n_out * 8));
@@ -313,7 +343,8 @@ template <class P>
 int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr, double lr,
                double lr_z, const double* Xt, const double* yt, int64_t nt, int flags,
                double* theta_out, double* z_out, double* values, double* thetas, double* obj,
-               double* mu, double* var, double* sc, int* info, int* steps_done) {
+               double* mu, double* var, double* sc, int* info, int* steps_done,
+               const Va* va = nullptr) {
   if (int rc = bind(ctx)) return rc;
   if (int rc = check_problem(ctx, path, a)) return rc;
   ARGCHK(theta_out && (!kFitc<P> || z_out) && info && steps_done, "NULL argument");
@@ -321,6 +352,13 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   ARGCHK(std::isfinite(lr), "batch: lr must be finite");
   if (kFitc<P>) ARGCHK(std::isfinite(lr_z), "batch: lr_z must be finite");
   ARGCHK(nt >= 0 && nt <= (1 << 24), "batch: nt must be in 0..2^24");
+  if (va) {
+    ARGCHK(va->nv >= 1 && va->nv <= (1 << 24), "batch: nv must be in 1..2^24");
+    ARGCHK(va->va_every >= 1 && va->va_every <= (1 << 20), "batch: va_every must be in 1..2^20");
+    ARGCHK(va->Xv, "batch: Xv is NULL, a validated fit needs its validation rows");
+    ARGCHK(va->yv, "batch: yv is NULL, a validated fit needs its validation targets");
+    ARGCHK(va->va_sc, "batch: va_sc is NULL, a validated fit needs room for its score rows");
+  }
   ARGCHK((flags & ~GPS_BATCH_STALE_NOISE) == 0, "unknown batch flag");
   if (path.es)
     ARGCHK(a.draw_sets <= std::max<int64_t>(itr, 1), "batch: draw_sets must be at most max(itr, 1)");
@@ -328,15 +366,19 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   if (!pred) nt = 0;
   const bool scored = pred && yt != nullptr;
   const int64_t nprob = a.nprob, nth = 2 + a.n_ell, nz = (int64_t)a.m * a.d;
+  // the validation rows and the rows of va_sc: the checkpoints and the final pass
+  const int64_t nv = va ? va->nv : 0;
+  const int64_t nva = va ? (itr + va->va_every - 1) / va->va_every + 1 : 0;
   const int64_t n_in =
-      nprob * a.n * (a.d + 1) + nprob * nt * (a.d + 1) + nprob * nz + a.n_draws();
-  const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC);
+      nprob * a.n * (a.d + 1) + nprob * (nt + nv) * (a.d + 1) + nprob * nz + a.n_draws();
+  const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC) +
+                        nprob * nva * GPS_N_SC;
   const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold, a.num_sim) : 0;
   const int64_t n_ws = nprob * stride;
   ARGCHK(n_in <= kMaxDoubles && n_out <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
   P p;
   double* ws;
-  if (int rc = carve(ctx, path, a, nt, n_out, n_ws, p, &ws)) return rc;
+  if (int rc = carve(ctx, path, a, nt, n_out, n_ws, p, &ws, nv)) return rc;
   p.mode = BATCH_MODE_TRAIN;
   p.itr = (int)itr;
   p.lr = lr;
@@ -352,9 +394,24 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   p.mu = p.obj + nprob * GPS_N_OBJ;
   p.var = p.mu + nprob * nt;
   p.sc = p.var + nprob * nt;
+  if constexpr (!kFitc<P>)
+    if (va) {  // Xv | yv behind the test rows and the draws, va_sc behind sc
+      p.xv = xt_dev + nprob * nt * (a.d + 1) + a.n_draws();
+      p.yv = p.xv + nprob * nv * a.d;
+      p.nv = (int)nv;
+      p.va_every = (int)va->va_every;
+      p.va_sc = p.sc + nprob * GPS_N_SC;
+    }
   std::vector<double> stale((size_t)nprob);  // before any step: θ0's own noise
   for (int64_t q = 0; q < nprob; ++q) stale[(size_t)q] = a.theta[q * nth + nth - 1];
   if (int rc = upload(ctx, a, p, Xt, yt, stale.data())) return rc;
+  if constexpr (!kFitc<P>)
+    if (va) {
+      HIPCHK(hipMemcpyAsync((void*)p.xv, va->Xv, (size_t)(nprob * nv * a.d) * 8,
+                            hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync((void*)p.yv, va->yv, (size_t)(nprob * nv) * 8,
+                            hipMemcpyHostToDevice, ctx->stream));
+    }
   {
     // no launch runs more than path.steps(n) steps; θ, Z, the stale σ², info and steps_done stay
     // in device memory between the launches, the last one adds the final pass
@@ -382,6 +439,9 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   if (int rc = download(ctx, mu, p.mu, nprob * nt)) return rc;
   if (int rc = download(ctx, var, p.var, nprob * nt)) return rc;
   if (int rc = download(ctx, scored ? sc : nullptr, p.sc, nprob * GPS_N_SC)) return rc;
+  if constexpr (!kFitc<P>)
+    if (va)
+      if (int rc = download(ctx, va->va_sc, p.va_sc, nprob * nva * GPS_N_SC)) return rc;
   if (int rc = download(ctx, info, p.info, nprob)) return rc;
   if (int rc = download(ctx, steps_done, p.steps_done, nprob)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -445,6 +505,35 @@ int gps_full_blockloo_train_tall(gps_ctx* ctx, int kind, int objective, int nfol
                     {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell, nfold}, itr, lr,
                     0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu, var, sc,
                     info, steps_done);
+}
+
+int gps_full_train_tall_va(gps_ctx* ctx, int kind, int objective, int64_t nprob, const double* X,
+                           const double* y, int64_t n, int d, const double* theta0, int n_ell,
+                           int64_t itr, double lr, const double* Xv, const double* yv, int64_t nv,
+                           int64_t va_every, const double* Xt, const double* yt, int64_t nt,
+                           int flags, double* theta_out, double* values, double* thetas,
+                           double* obj, double* mu, double* var, double* sc, double* va_sc,
+                           int* info, int* steps_done) {
+  const Va va = {Xv, yv, nv, va_every, va_sc};
+  return train_call(ctx, kFullTallVa,
+                    {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell}, itr, lr, 0.0,
+                    Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu, var, sc, info,
+                    steps_done, &va);
+}
+
+int gps_full_blockloo_train_tall_va(gps_ctx* ctx, int kind, int objective, int nfold,
+                                    int64_t nprob, const double* X, const double* y, int64_t n,
+                                    int d, const double* theta0, int n_ell, int64_t itr, double lr,
+                                    const double* Xv, const double* yv, int64_t nv,
+                                    int64_t va_every, const double* Xt, const double* yt,
+                                    int64_t nt, int flags, double* theta_out, double* values,
+                                    double* thetas, double* obj, double* mu, double* var,
+                                    double* sc, double* va_sc, int* info, int* steps_done) {
+  const Va va = {Xv, yv, nv, va_every, va_sc};
+  return train_call(ctx, kFullTallBlockVa,
+                    {kind, objective, nprob, X, y, n, d, nullptr, 0, theta0, n_ell, nfold}, itr, lr,
+                    0.0, Xt, yt, nt, flags, theta_out, nullptr, values, thetas, obj, mu, var, sc,
+                    info, steps_done, &va);
 }
 
 int gps_full_es_grad_tall(gps_ctx* ctx, int kind, int nfold, int num_sim, double beta,

@@ -96,6 +96,11 @@ inline bool full_tall_args_ok(const BatchParams& p, int (*steps)(int64_t n), con
          !(reinterpret_cast<uintptr_t>(ws) & 31);
 }
 
+// what the two VA launchers check on top of it: a training launch with validation rows (§34)
+inline bool full_tall_va_args_ok(const BatchParams& p) {
+  return p.mode == BATCH_MODE_TRAIN && p.xv && p.yv && p.va_sc && p.nv >= 1 && p.va_every >= 1;
+}
+
 // ------------------------------------------------------------------ the fold geometry (§26, §32)
 // the tile-aligned column range [klo, khi) that the folds of row tile bi's live rows cover
 __device__ __forceinline__ void fold_span(int bi, int n, int nfold, int& klo, int& khi) {
@@ -663,11 +668,111 @@ __device__ __forceinline__ int block_gradient(const Lds& s, const double* x, dou
                                               int objective, int nfold, double sf2,
                                               double (&g)[BG], double& value, double* fold_values);
 
+// The predictive at `cnt` rows `rows` ([cnt][d]) after forward(): X in W1, α in LDS, W0 free (L is
+// dead).  Rows in blocks of T: K*ᵀ (np×T, zero in the padding) into the first T columns of W0, V =
+// X K*ᵀ tile by tile, μ* = k*·α, var* = σ² + sf² − the column norms of V; thread (grp, c) sums the
+// rows of column c that fall to its group, the four groups are added in order.  μ* / var* go to
+// mu / var where given, and with targets `yr` each row's six score terms are added to thread c's
+// sums.  This is the final pass's test-row loop in tall_body (which keeps its own copy of the text,
+// as forward() keeps factor_invert's: the VA = false kernels are to compile as they did, DESIGN
+// §34) — keep the two in step, a validation row is bitwise a test row of an itr = 0 call.  Scratch:
+// s.tile, s.pan and those columns of W0; nothing either gradient reads.  The caller arrives
+// synchronised; ends synchronised.
+__device__ __forceinline__ void predict_rows(const Lds& s, const double* x, double* W0,
+                                             const double* W1, int n, int np, int d, double sf2,
+                                             double sn2, const double* rows, const double* yr,
+                                             int cnt, double* mu_out, double* var_out, double ymean,
+                                             double yvar, double triv_c, double (&sums)[6]) {
+  const int t = threadIdx.x, nb = np / T, dp = d | 1;
+  const int64_t ld = np;
+  const double* il = s.th + 20;
+  const int grp = t >> 6, c = t & 63;
+  double* fi = s.pan;
+  double* fj = s.pan + T * dp;
+  for (int c0 = 0; c0 < cnt; c0 += T) {
+    const int ntb = min(T, cnt - c0);
+    for (int bi = 0; bi < nb; ++bi) {
+      stage_feat(fi, x, bi * T, n - bi * T, d, dp);
+      stage_feat(fj, rows, c0, ntb, d, dp);
+      __syncthreads();
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = acc_row(mi, r), gi = bi * T + row;
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni) {
+            const int col = acc_col(ni);
+            W0[gi * ld + col] = gi < n && col < ntb
+                ? sf2 * exp(-0.5 * sqdist(fi + row * dp, fj + col * dp, il, d)) : 0.0;
+          }
+        }
+      __syncthreads();
+    }
+    double mu = 0.0, q = 0.0;
+    for (int i = grp; i < n; i += BT / 64) mu = fma(W0[i * ld + c], s.alpha[i], mu);
+    for (int bi = 0; bi < nb; ++bi) {
+      d4 acc[2][2];
+      acc_zero(acc);
+      tile_mma<XMAJ, KMAJ, false>(acc, W1 + bi * T * ld, ld, W0, ld, 0, (bi + 1) * T, nullptr,
+                                  s.pan);
+      acc_store<false>(acc, s.tile, TL, 1.0);
+      __syncthreads();
+      for (int r = grp * 16; r < grp * 16 + 16; ++r) {
+        const double vv = s.tile[r * TL + c];
+        q = fma(vv, vv, q);
+      }
+      __syncthreads();
+    }
+    s.tile[t] = mu;
+    s.tile[BT + t] = q;
+    __syncthreads();
+    if (t < ntb) {
+      double m = 0.0, qq = 0.0;
+      for (int w = 0; w < BT / 64; ++w) {
+        m += s.tile[w * 64 + t];
+        qq += s.tile[BT + w * 64 + t];
+      }
+      const double cv = (sn2 + sf2) - qq;
+      if (mu_out) {
+        mu_out[c0 + t] = m;
+        var_out[c0 + t] = cv;
+      }
+      if (yr) {
+        const double yv = yr[c0 + t];
+        score_row_add(sums, m, cv, yv, ymean, yvar, triv_c);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// batch_driver.h's scores_store with the destination and the row count as parameters: the block's
+// six sums → six GPS_SC_* entries at sc (one thread)
+__device__ __forceinline__ void scores_store_to(double* sc, double cnt, const double (&tot)[6]) {
+  sc[GPS_SC_CRPS] = tot[0] / cnt;
+  sc[GPS_SC_LOGS] = tot[1] / cnt;
+  sc[GPS_SC_MSLL] = tot[2] / cnt;
+  sc[GPS_SC_SMSE] = tot[3] / tot[4];
+  sc[GPS_SC_MSE] = tot[3] / cnt;
+  sc[GPS_SC_COVER] = tot[5] / cnt;
+}
+
 // A kernel's whole body: the SGD loop (or the one evaluation of BATCH_MODE_GRAD), the final pass
 // and the outputs.  BLOCK: the objective is GPS_BLOCK_DSS / GPS_BLOCK_KC over nfold folds, the
 // workspace has a third array behind W1 (w1 doubles), and BATCH_MODE_GRAD also writes value and
 // fold_values; without it those four arguments are unused.
-template <bool BLOCK>
+//
+// VA (BATCH_MODE_TRAIN only): the problem's validation rows p.xv / p.yv (nv of them)
+// are scored inside the fit.  A training step whose global index i = step0 + st is a multiple of
+// p.va_every is a checkpoint: between forward() and the gradient — X in W1, α in LDS, W0 free until
+// the gradient rebuilds it — predict_rows forms the predictive at the validation rows at that
+// forward's parameters (θ before step i, its own σ²) and the six GPS_SC_* entries go to
+// va_sc[pb][i / va_every].  The final pass adds row nva − 1 (nva = ceil(itr / va_every) + 1) at its
+// own parameters (so with stale_noise its σ² is the stale one), then the test rows; both run
+// inside the step loop, through the one call of predict_rows.  A failed problem gets NaN in every
+// row from the first checkpoint it did not reach.  Without VA the body is the text it was.
+template <bool BLOCK, bool VA = false>
 __device__ __forceinline__ void tall_body(const BatchParams& p, double* ws, int64_t ws_stride,
                                           int nfold, int64_t w1, double* value,
                                           double* fold_values) {
@@ -695,6 +800,19 @@ __device__ __forceinline__ void tall_body(const BatchParams& p, double* ws, int6
   const int ntrain = p.mode == BATCH_MODE_GRAD ? 1 : p.nsteps;
   const int neval = ntrain + (p.mode == BATCH_MODE_TRAIN && p.do_final ? 1 : 0);
   double sf2 = 0.0, sn2 = 0.0;
+  // VA: the train-target mean and unbiased variance once a launch, in gps_full_set_data's order
+  // (the final pass's own lines below), and the first step whose checkpoint is still to come
+  [[maybe_unused]] double va_ymean = 0.0, va_yvar = 0.0, va_triv = 0.0;
+  [[maybe_unused]] int va_reach = done > p.step0 ? done : p.step0;
+  if constexpr (VA) {
+    __syncthreads();  // y is visible
+    double ysum = 0.0, yss = 0.0;
+    for (int i = 0; i < n; ++i) ysum += s.y[i];
+    va_ymean = ysum / n;
+    for (int i = 0; i < n; ++i) yss += (s.y[i] - va_ymean) * (s.y[i] - va_ymean);
+    va_yvar = yss / (n - 1);
+    va_triv = 0.5 * log(6.28318530717958647692 * va_yvar);
+  }
   for (int st = 0; st < neval && info == 0; ++st) {
     const bool fin = st == ntrain;
     __syncthreads();  // θ (loaded, or the previous step's update) is visible
@@ -706,6 +824,31 @@ __device__ __forceinline__ void tall_body(const BatchParams& p, double* ws, int6
     __syncthreads();
     if (!fin) stale = lsn;
     info = forward(s, x, W0, W1, n, np, d, sf2, sn2, obj);
+    if constexpr (VA) {
+      // a checkpoint's validation rows (sums only); in the final pass the last validation row,
+      // then the test rows (μ / var stored, scored with yt)
+      const int gi = p.step0 + st;
+      const int64_t nva = (p.itr + p.va_every - 1) / p.va_every + 1;
+      const bool pred = p.xt != nullptr && p.nt > 0;
+      const int npass = info ? 0 : fin ? (pred ? 2 : 1) : gi % p.va_every == 0 ? 1 : 0;
+      for (int ps = 0; ps < npass; ++ps) {
+        const bool te = ps == 1;
+        const double* yr = te ? (p.yt ? p.yt + pb * p.nt : nullptr) : p.yv + pb * p.nv;
+        const int cnt = te ? p.nt : p.nv;
+        double sums[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // as score_rows_kernel; thread c's rows
+        predict_rows(s, x, W0, W1, n, np, d, sf2, sn2,
+                     te ? p.xt + pb * p.nt * d : p.xv + pb * p.nv * d, yr, cnt,
+                     te ? p.mu + pb * p.nt : nullptr, te ? p.var + pb * p.nt : nullptr, va_ymean,
+                     va_yvar, va_triv, sums);
+        if (!yr) continue;
+        block_sum<6>(sums, s.sh);
+        if (t == 0)
+          scores_store_to(te ? p.sc + pb * GPS_N_SC
+                             : p.va_sc + (pb * nva + (fin ? nva - 1 : gi / p.va_every)) * GPS_N_SC,
+                          (double)cnt, sums);
+      }
+      if (!info && !fin) va_reach = gi + 1;
+    }
     if (info || fin) break;
     double g[BG];
     double bval = 0.0;
@@ -772,6 +915,20 @@ __device__ __forceinline__ void tall_body(const BatchParams& p, double* ws, int6
   }
   train_write_back<BT>(p, pb, t, s.th, nullptr, info, done, stale);
   if (t == 0) p.info[pb] = info;
+  if constexpr (VA) {
+    // a failed problem (in this launch or an earlier one): NaN in this launch's checkpoint rows
+    // from the first it did not reach, and in the final row; train_write_back's rule for values
+    if (info) {
+      const int64_t nva = (p.itr + p.va_every - 1) / p.va_every + 1;
+      const int64_t r0 = (va_reach + p.va_every - 1) / p.va_every;
+      const int64_t r1 = p.do_final ? nva : (p.step0 + p.nsteps + p.va_every - 1) / p.va_every;
+      for (int64_t e = r0 * GPS_N_SC + t; e < r1 * GPS_N_SC; e += BT)
+        p.va_sc[pb * nva * GPS_N_SC + e] = batch_nan();
+    }
+    // the final pass's rows ran inside the step loop
+    if (p.do_final) final_outputs<BT>(p, pb, t, info, p.xt != nullptr && p.nt > 0, obj);
+    return;
+  }
   if (!p.do_final) return;
   const bool pred = p.xt != nullptr && p.nt > 0;
   if (!final_outputs<BT>(p, pb, t, info, pred, obj)) return;

@@ -272,6 +272,14 @@ struct SurfaceParams {
 constexpr int kBatchStepsPerLaunch = 64;  // SGD steps one launch may run
 enum { BATCH_MODE_GRAD = 0, BATCH_MODE_TRAIN = 1 };
 struct BatchParams {
+  // the validation rows the tall full-GP VA kernels score inside the fit; every other
+  // launcher ignores them.  They stand in FRONT: a tall kernel's arguments are this struct and its
+  // workspace behind it, and the compiler fetches `sc` and the workspace pointer in one load; new
+  // members between the two changed the register allocation of the kernels that never read them
+  // (5 and 11 more SGPR spills), in front every kernel argument moves by 32 bytes and nothing else
+  const double* xv; const double* yv; int nv;   // [nprob][nv][d], [nprob][nv]
+  int va_every;                       // step i is a checkpoint when i % va_every == 0
+  double* va_sc;                      // [nprob][ceil(itr / va_every) + 1][GPS_N_SC]
   const double* x; const double* y;   // [nprob][n][d], [nprob][n]
   int nprob, n, d, n_ell, kind, objective, mode;
   // per-problem state, kept on the device between the launches of one call
@@ -385,6 +393,9 @@ int64_t batch_full_tall_ws_doubles(int64_t n);
 // 500): a function of n alone
 int batch_full_tall_steps(int64_t n);
 hipError_t launch_batch_full_tall(const BatchFullTallParams& p, hipStream_t s);
+// the same launch with b.xv / b.yv scored at the checkpoints and in the final pass (b.va_sc;
+// BATCH_MODE_TRAIN only): refuses a NULL xv, yv or va_sc, nv < 1 and va_every < 1
+hipError_t launch_batch_full_tall_va(const BatchFullTallParams& p, hipStream_t s);
 
 // the same batches on the block-LOO objectives GPS_BLOCK_DSS / GPS_BLOCK_KC over nfold folds
 // (kernels_batch_full_tall_block.hip): b.objective is the GPS_BLOCK_* code, everything
@@ -405,6 +416,8 @@ struct BatchFullTallBlockParams {
 // LDS is batch_full_tall_lds_bytes(n) and a launch runs batch_full_tall_steps(n) steps: §24's
 int64_t batch_full_tall_block_ws_doubles(int64_t n, int nfold);
 hipError_t launch_batch_full_tall_block(const BatchFullTallBlockParams& p, hipStream_t s);
+// with the validation rows, as launch_batch_full_tall_va
+hipError_t launch_batch_full_tall_block_va(const BatchFullTallBlockParams& p, hipStream_t s);
 
 // Scaled Newton–Schulz schedule for a spectrum of C/s inside [x0, 1] (api_block.hip's comment at
 // ns_schedule has the derivation): β per step into beta[0..cap), host and device.  At most

@@ -14,6 +14,11 @@ __global__ __launch_bounds__(BT) void batch_full_tall_kernel(BatchFullTallParams
   tall_body<false>(tp.b, tp.ws, tp.ws_stride, 0, 0, nullptr, nullptr);
 }
 
+// the same fit with the validation rows scored at the checkpoints
+__global__ __launch_bounds__(BT) void batch_full_tall_va_kernel(BatchFullTallParams tp) {
+  tall_body<false, true>(tp.b, tp.ws, tp.ws_stride, 0, 0, nullptr, nullptr);
+}
+
 }  // namespace
 
 size_t batch_full_tall_lds_bytes(int n) {
@@ -41,6 +46,20 @@ hipError_t launch_batch_full_tall(const BatchFullTallParams& tp, hipStream_t s) 
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(batch_full_tall_kernel, dim3((unsigned)p.nprob), dim3(BT),
                      batch_full_tall_lds_bytes(p.n), s, tp);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_full_tall_va(const BatchFullTallParams& tp, hipStream_t s) {
+  const BatchParams& p = tp.b;
+  if (!full_tall_va_args_ok(p) ||
+      !full_tall_args_ok(p, batch_full_tall_steps, tp.ws, tp.ws_stride,
+                         batch_full_tall_ws_doubles(p.n)))
+    return hipErrorInvalidValue;
+  const hipError_t e = raise_dynamic_lds((const void*)batch_full_tall_va_kernel,
+                                         batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(batch_full_tall_va_kernel, dim3((unsigned)p.nprob), dim3(BT),
+                     batch_full_tall_lds_bytes(p.n), s, tp);  // LDS and workspace as without
   return hipGetLastError();
 }
 

@@ -165,6 +165,11 @@ __global__ __launch_bounds__(BT) void batch_full_tall_block_kernel(BatchFullTall
   tall_body<true>(tp.b, tp.ws, tp.ws_stride, tp.nfold, tp.w1, tp.value, tp.fold_values);
 }
 
+// the same fit with the validation rows scored at the checkpoints
+__global__ __launch_bounds__(BT) void batch_full_tall_block_va_kernel(BatchFullTallBlockParams tp) {
+  tall_body<true, true>(tp.b, tp.ws, tp.ws_stride, tp.nfold, tp.w1, tp.value, tp.fold_values);
+}
+
 // W1's doubles: X, then the fold scratch, then Y
 int64_t w1_doubles(int64_t n, int nfold) {
   const int64_t np = padded(n), bp = padded((n + nfold - 1) / nfold);
@@ -178,22 +183,43 @@ int64_t batch_full_tall_block_ws_doubles(int64_t n, int nfold) {
   return 2 * np * np + w1_doubles(n, nfold);
 }
 
+namespace {
+
+// what both launchers refuse (the fold count first: the workspace size divides by it)
+bool block_args_ok(const BatchFullTallBlockParams& tp) {
+  const BatchParams& p = tp.b;
+  return !(tp.nfold < 2 || tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
+           (p.objective != GPS_BLOCK_DSS && p.objective != GPS_BLOCK_KC) ||
+           (p.mode == BATCH_MODE_GRAD && !tp.value) ||
+           !full_tall_args_ok(p, batch_full_tall_steps, tp.ws, tp.ws_stride,
+                              batch_full_tall_block_ws_doubles(p.n, tp.nfold)));
+}
+
+}  // namespace
+
 hipError_t launch_batch_full_tall_block(const BatchFullTallBlockParams& tq, hipStream_t s) {
   BatchFullTallBlockParams tp = tq;
   const BatchParams& p = tp.b;
-  // (the fold count first: the workspace size divides by it)
-  if (tp.nfold < 2 || tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
-      (p.objective != GPS_BLOCK_DSS && p.objective != GPS_BLOCK_KC) ||
-      (p.mode == BATCH_MODE_GRAD && !tp.value) ||
-      !full_tall_args_ok(p, batch_full_tall_steps, tp.ws, tp.ws_stride,
-                         batch_full_tall_block_ws_doubles(p.n, tp.nfold)))
-    return hipErrorInvalidValue;
+  if (!block_args_ok(tp)) return hipErrorInvalidValue;
   tp.w1 = w1_doubles(p.n, tp.nfold);
   const hipError_t e = raise_dynamic_lds((const void*)batch_full_tall_block_kernel,
                                          batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(batch_full_tall_block_kernel, dim3((unsigned)p.nprob), dim3(BT),
                      batch_full_tall_lds_bytes(p.n), s, tp);  // §24's LDS layout unchanged
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_full_tall_block_va(const BatchFullTallBlockParams& tq, hipStream_t s) {
+  BatchFullTallBlockParams tp = tq;
+  const BatchParams& p = tp.b;
+  if (!block_args_ok(tp) || !full_tall_va_args_ok(p)) return hipErrorInvalidValue;
+  tp.w1 = w1_doubles(p.n, tp.nfold);
+  const hipError_t e = raise_dynamic_lds((const void*)batch_full_tall_block_va_kernel,
+                                         batch_full_tall_lds_bytes(GPS_BATCH_FULL_TALL_MAX_N));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(batch_full_tall_block_va_kernel, dim3((unsigned)p.nprob), dim3(BT),
+                     batch_full_tall_lds_bytes(p.n), s, tp);  // LDS and workspace as without
   return hipGetLastError();
 }
 

@@ -175,6 +175,13 @@ SIGNATURES = {
     "gps_full_blockloo_train_tall": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_i64, _P, _P, _c_i64,
                                               _c_int, _P, _c_int, _c_i64, _c_dbl, _P, _P, _c_i64,
                                               _c_int, _P, _P, _P, _P, _P, _P, _P, _PI, _PI]),
+    "gps_full_train_tall_va": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P,
+                                        _c_int, _c_i64, _c_dbl, _P, _P, _c_i64, _c_i64, _P, _P,
+                                        _c_i64, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _PI, _PI]),
+    "gps_full_blockloo_train_tall_va": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_i64, _P, _P,
+                                                 _c_i64, _c_int, _P, _c_int, _c_i64, _c_dbl, _P, _P,
+                                                 _c_i64, _c_i64, _P, _P, _c_i64, _c_int, _P, _P, _P,
+                                                 _P, _P, _P, _P, _P, _PI, _PI]),
     "gps_full_es_grad_tall": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_dbl, _c_i64, _P, _P, _c_i64,
                                        _c_int, _P, _c_int, _P, _P, _P, _P, _P, _PI]),
     "gps_full_es_train_tall": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_dbl, _c_i64, _P, _P,

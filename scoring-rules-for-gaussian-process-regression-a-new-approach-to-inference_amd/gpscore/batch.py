@@ -1,6 +1,7 @@
 """Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
 (DESIGN §19, §20), and their siblings for taller problems (§22, §24; the block-LOO DSS / KC
-objectives §26 for the full GP, §27 for FITC; the block-LOO energy score §32).
+objectives §26 for the full GP, §27 for FITC; the block-LOO energy score §32; a validation set
+scored inside the tall full-GP fits §34).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
@@ -10,6 +11,7 @@ objectives §26 for the full GP, §27 for FITC; the block-LOO energy score §32)
     res = gpscore.train_tall(X, y, theta0, "loo_crps", lr=1.0, itr=400, Xt=Xt, yt=yt)  # n <= 512
     res = gpscore.blockloo_train_tall(X, y, theta0, "dss", nfold=4, lr=1e-3, itr=150, Xt=Xt, yt=yt)
     res = gpscore.es_train_tall(X, y, theta0, nfold=4, num_sim=300, lr=0.1, itr=25, Xt=Xt, yt=yt)
+    res = gpscore.train_tall_validated(X, y, theta0, Xv, yv, "loo_crps", itr=400, select="crps")  # §34
     res = gpscore.fitc_blockloo_train_tall(X, y, Z0, theta0, "kc", nfold=4, lr=0.1, itr=3000,
                                            Xt=Xt, yt=yt)                                # n <= 2048
 
@@ -239,15 +241,19 @@ class _Path:
     max_n: int
     fitc: bool = False
     rule: str = "point"
+    va: bool = False  # the training entry takes a validation set and returns its score rows (§34)
 
 
-_FULL = _Path("gps_full_grad_batch", "gps_full_train_batch", BATCH_MAX_N)
+_FULL =_Path("gps_full_grad_batch", "gps_full_train_batch", BATCH_MAX_N)
 _FULL_TALL = _Path("gps_full_grad_tall", "gps_full_train_tall", BATCH_FULL_TALL_MAX_N)
 _FULL_BLOCK = _Path("gps_full_blockloo_grad_tall", "gps_full_blockloo_train_tall",
                     BATCH_FULL_TALL_MAX_N, rule="block")
 _FULL_ES = _Path("gps_full_es_grad_tall", "gps_full_es_train_tall", BATCH_FULL_TALL_MAX_N,
                  rule="es")
-_FITC = _Path("gps_fitc_grad_batch", "gps_fitc_train_batch", BATCH_MAX_N, fitc=True)
+_FULL_TALL_VA = _Path("gps_full_grad_tall", "gps_full_train_tall_va", BATCH_FULL_TALL_MAX_N, va=True)
+_FULL_BLOCK_VA = _Path("gps_full_blockloo_grad_tall", "gps_full_blockloo_train_tall_va",
+                       BATCH_FULL_TALL_MAX_N, rule="block", va=True)
+_FITC = _Path("gps_fitc_grad_batch","gps_fitc_train_batch", BATCH_MAX_N, fitc=True)
 _FITC_TALL = _Path("gps_fitc_grad_tall", "gps_fitc_train_tall", BATCH_FITC_TALL_MAX_N, fitc=True)
 _FITC_BLOCK = _Path("gps_fitc_blockloo_grad_tall", "gps_fitc_blockloo_train_tall",
                     BATCH_FITC_TALL_MAX_N, fitc=True, rule="block")
@@ -274,7 +280,7 @@ def _front(path, X, y, Z, theta, objective, nfold, num_sim, beta, rbf):
     lead = (() if path.fitc else (GPS_RBF if rbf else GPS_ARD,)) + head \
         + (B, ptr(X), ptr(y), n, d) + ((ptr(Z), m) if path.fitc else ()) + (ptr(th), n_ell)
     return SimpleNamespace(lead=lead, B=B, n=n, d=d, m=m, n_ell=n_ell, nfold=nfold,
-                           num_sim=num_sim)
+                           num_sim=num_sim, th=th)
 
 
 def _objectives(obj):
@@ -303,10 +309,97 @@ def _grad(path, X, y, Z, theta, objective=None, nfold=None, num_sim=None, beta=N
         + ((fold,) if folds else ()) + (objs, info)
 
 
+SELECT_METRICS = ("crps", "logs", "msll", "smse", "mse")  # validation scores a fit can be selected on
+
+
+@dataclass
+class ValidatedTrainResult(BatchTrainResult):
+    """train_tall_validated's outputs: BatchTrainResult's fields, ``va_steps`` (nva,) the step index
+    of each validation row — 0, va_every, 2·va_every, ... below itr, then itr for the final pass —
+    and ``va_scores`` {name: (B, nva)} over SCORE_NAMES, the validation set's score bundle at the
+    parameters of that step's forward (θ before the step; the last row at the final pass's).  With
+    ``select``: ``best_step`` (B,) the va_steps entry of the smallest finite score (the earliest
+    wins a tie; −1 when no row is finite) and ``theta_best`` (B, 2 + n_ell) the θ that row was
+    evaluated at (NaN where best_step is −1); None without."""
+    va_steps: np.ndarray = None
+    va_scores: dict = None
+    best_step: np.ndarray | None = None
+    theta_best: np.ndarray | None = None
+
+
+def _va_every(va_every):
+    if isinstance(va_every, bool) or not isinstance(va_every, (int, np.integer)) or va_every < 1:
+        raise ValueError(f"va_every must be a positive integer, got {va_every!r}")
+    return int(va_every)
+
+
+def _select_metric(select):
+    if select is not None and select not in SELECT_METRICS:
+        raise ValueError(f"select must be None or one of {SELECT_METRICS} (all lower-is-better; "
+                         f"'cover' is a calibration figure, not a score to minimise), got "
+                         f"{select!r}")
+    return select
+
+
+def _valids(Xv, yv, B, d):
+    """(Xv (B, nv, d), yv (B, nv), nv) checked against the batch as _tests checks Xt / yt; both are
+    mandatory."""
+    if Xv is None:
+        raise ValueError("Xv is required: the validation rows, (B, nv, d)")
+    if yv is None:
+        raise ValueError("yv is required: a validation set is scored against its targets")
+    try:
+        Xv = f64(Xv)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"Xv must be a rectangular array: {e}") from None
+    if Xv.ndim == 2 and d == 1:
+        Xv = Xv[:, :, None]
+    if Xv.ndim != 3 or Xv.shape[0] != B or Xv.shape[2] != d:
+        raise ValueError(f"Xv must be (B, nv, d) = ({B}, nv, {d}), got {Xv.shape}")
+    Xv = np.ascontiguousarray(Xv)
+    nv = Xv.shape[1]
+    if nv < 1:
+        raise ValueError("Xv holds no rows")
+    try:
+        yv = f64(yv)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"yv must be a rectangular array: {e}") from None
+    if yv.shape != (B, nv):
+        raise ValueError(f"yv must be (B, nv) = ({B}, {nv}), got {yv.shape}")
+    return Xv, np.ascontiguousarray(yv), nv
+
+
+def va_steps_of(itr, va_every):
+    """The step index of each validation row of a fit of ``itr`` steps: the checkpoints 0, va_every,
+    ... below itr, then itr (the final pass): ceil(itr / va_every) + 1 rows."""
+    return np.concatenate([np.arange(0, itr, va_every), [itr]]).astype(np.int64)
+
+
+def select_best(va_row, va_steps, theta0, thetas, theta):
+    """Host arithmetic of ``select``: ``va_row`` (B, nva) one lower-is-better score per validation
+    row → (best_step (B,), theta_best (B, nth)).  The smallest finite entry wins, the earliest on a
+    tie; the θ of row r is theta0 for step 0, thetas[:, i − 1] for checkpoint step i and ``theta``
+    for the last row (the final pass).  No finite row: −1 and NaN."""
+    va_row = np.asarray(va_row, dtype=np.float64)
+    B, nva = va_row.shape
+    best = np.full(B, -1, np.int64)
+    th = np.full((B, theta0.shape[1]), np.nan)
+    for q in range(B):
+        ok = np.isfinite(va_row[q])
+        if not ok.any():
+            continue
+        r = int(np.argmin(np.where(ok, va_row[q], np.inf)))  # argmin: the first of equal minima
+        best[q] = va_steps[r]
+        th[q] = theta[q] if r == nva - 1 else theta0[q] if va_steps[r] == 0 \
+            else thetas[q, va_steps[r] - 1]
+    return best, th
+
+
 def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, beta=None, lr=1.0,
            lr_z=None, itr=400, draws=None, draw_sets=None, rng=None, Xt=None, yt=None, rbf=False,
-           stale_noise=False, ctx=None):
-    """A path's training call: BatchTrainResult, or FitcBatchTrainResult on a FITC path."""
+           stale_noise=False, ctx=None, Xv=None, yv=None, va_every=1, select=None):
+    """A path's training call: BatchTrainResult, FitcBatchTrainResult on a FITC path, or
+    ValidatedTrainResult on a path with a validation set (path.va: Xv, yv, va_every, select)."""
     f = _front(path, X, y, Z0, theta0, objective, nfold, num_sim, beta, rbf)
     B, es = f.B, path.rule == "es"
     itr, lr = _steps(itr, lr)
@@ -321,6 +414,12 @@ def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, bet
                              f"draw sets")
         sets = int(sets)
     Xt, yt, nt = _tests(Xt, yt, B, f.d)
+    if path.va:
+        Xv, yv, nv = _valids(Xv, yv, B, f.d)
+        va_every = _va_every(va_every)
+        select = _select_metric(select)
+        va_steps = va_steps_of(itr, va_every)
+        va_sc = np.empty((B, len(va_steps), len(SCORE_NAMES)))
     if es:
         draws = _es_draws(draws, B, sets, f.n, f.nfold, f.num_sim, rng)
     ctx = ctx or _lib.default_context()
@@ -333,15 +432,23 @@ def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, bet
     var = np.empty((B, nt)) if nt else None
     sc = np.empty((B, len(SCORE_NAMES))) if yt is not None else None
     info, steps = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    ctx.call(path.train, *f.lead, itr, lr, *((lr_z,) if path.fitc else ()), ptr(Xt), ptr(yt), nt,
+    ctx.call(path.train, *f.lead, itr, lr, *((lr_z,) if path.fitc else ()),
+             *((ptr(Xv), ptr(yv), nv, va_every) if path.va else ()), ptr(Xt), ptr(yt), nt,
              GPS_BATCH_STALE_NOISE if stale_noise else 0, *((ptr(draws), sets) if es else ()),
              ptr(theta), *((ptr(Z),) if path.fitc else ()), ptr(values), ptr(thetas), ptr(obj),
-             ptr(mu), ptr(var), ptr(sc), _iptr(info), _iptr(steps))
+             ptr(mu), ptr(var), ptr(sc), *((ptr(va_sc),) if path.va else ()), _iptr(info),
+             _iptr(steps))
     res = dict(theta=theta, series={"objective": values, "theta": thetas},
                objectives=_objectives(obj), mu=mu, var=var,
                scores=None if sc is None else {k: sc[:, q].copy()
                                                for q, k in enumerate(SCORE_NAMES)},
                info=info, steps_done=steps)
+    if path.va:
+        va_scores = {k: va_sc[:, :, q].copy() for q, k in enumerate(SCORE_NAMES)}
+        best, th_best = (None, None) if select is None else select_best(
+            va_scores["test_" + select], va_steps, f.th, thetas, theta)
+        return ValidatedTrainResult(va_steps=va_steps, va_scores=va_scores, best_step=best,
+                                    theta_best=th_best, **res)
     return FitcBatchTrainResult(Z=Z, **res) if path.fitc else BatchTrainResult(**res)
 
 
@@ -399,6 +506,36 @@ def blockloo_train_tall(X, y, theta0, objective="dss", nfold=4, lr=1e-3, itr=150
     BatchTrainResult."""
     return _train(_FULL_BLOCK, X, y, None, theta0, objective, nfold, lr=lr, itr=itr, Xt=Xt, yt=yt,
                   rbf=rbf, stale_noise=stale_noise, ctx=ctx)
+
+
+def train_tall_validated(X, y, theta0, Xv, yv, objective="loo_crps", lr=1.0, itr=400, va_every=1,
+                         select=None, Xt=None, yt=None, rbf=False, stale_noise=False, ctx=None):
+    """train_tall with a validation set scored inside the fit (one gps_full_train_tall_va call,
+    DESIGN §34): the per-iteration validation series "kin40k-FULL-compare.py" carries commented out
+    (KF:441-449), from the factorisation each step has in hand.  ``Xv`` (B, nv, d) or (B, nv), ``yv``
+    (B, nv), both mandatory; every step i with i % ``va_every`` == 0 scores them at that step's
+    forward (θ before the step, its own σ²: the model ``series["objective"][:, i]`` describes), and
+    the final pass adds one more row at its own parameters.  Under ``stale_noise`` that last row's
+    noise is the stale one — the σ² of the last step's forward, so with itr = k it is the scripts'
+    va_series[k − 1] — while ``theta_best`` for it is the final θ as returned.  ``select``: one of
+    "crps", "logs", "msll", "smse", "mse" (lower is better) picks each problem's best row on the
+    host.  The fit is bitwise train_tall's; everything else as there.  Returns
+    ValidatedTrainResult."""
+    return _train(_FULL_TALL_VA, X, y, None, theta0, objective, lr=lr, itr=itr, Xt=Xt, yt=yt,
+                  rbf=rbf, stale_noise=stale_noise, ctx=ctx, Xv=Xv, yv=yv, va_every=va_every,
+                  select=select)
+
+
+def blockloo_train_tall_validated(X, y, theta0, Xv, yv, objective="dss", nfold=4, lr=1e-3, itr=150,
+                                  va_every=1, select=None, Xt=None, yt=None, rbf=False,
+                                  stale_noise=False, ctx=None):
+    """blockloo_train_tall with a validation set scored inside the fit (one
+    gps_full_blockloo_train_tall_va call; the series KF:557-563 carries commented out,
+    its pointwise scores).  Validation arguments, ``select`` and ValidatedTrainResult as
+    train_tall_validated; the fit is bitwise blockloo_train_tall's."""
+    return _train(_FULL_BLOCK_VA, X, y, None, theta0, objective, nfold, lr=lr, itr=itr, Xt=Xt,
+                  yt=yt, rbf=rbf, stale_noise=stale_noise, ctx=ctx, Xv=Xv, yv=yv,
+                  va_every=va_every, select=select)
 
 
 def es_value_and_grad_tall(X, y, theta, nfold=4, num_sim=300, beta=1.0, draws=None, rng=None,

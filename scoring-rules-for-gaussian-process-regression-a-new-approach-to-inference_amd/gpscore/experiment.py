@@ -21,6 +21,8 @@ LOO-CRPS / NLML / LOO-LogS fits (full GP, n = 500) have a batch route as well: r
 train_tall call per method for all replicates; its block-LOO DSS fit goes through
 run_full_blockloo_batch, one blockloo_train_tall call for all replicates, and its ES fit through
 run_full_es_batch, one es_train_tall call: all five KF methods have a one-call-per-method route.
+run_full_validated_batch is run_full_batch / run_full_blockloo_batch with every replicate's
+validation split (KF:203-209) scored inside the fits, step by step (KF:441-449, commented out there).
 
 Every number here comes from gpscore.GP (libgpscore.so): the SGD loops are GP.train, the
 predictive and its scores GP.predict (run_simple: gpscore.batch.train_batch).  The workbook is not shipped (the scripts open it from
@@ -316,7 +318,8 @@ BATCH_OBJECTIVES = BATCH_OBJS  # what the batched pointwise kernels can fit
 
 
 def _run_batch(who, sheets, TT, methods, accepts, why, route, train, what, m=None, es=None,
-               zero_for=(), itr=None, seed=None, reseed=True, stale_noise=True, ctx=None):
+               zero_for=(), itr=None, seed=None, reseed=True, stale_noise=True, ctx=None,
+               post=None):
     """The replicate runner behind the run_*_batch functions (``who``: the caller's name in its
     messages).  Every method's objective must be in ``accepts``, else ValueError "<why>; use
     <route(objective)> for it".  Data replicates and starting points are drawn as run draws them:
@@ -325,7 +328,9 @@ def _run_batch(who, sheets, TT, methods, accepts, why, route, train, what, m=Non
     method, ``train(X, y, th0, Z0 or draws or None, method, lr=, itr=, Xt=, yt=, stale_noise=,
     ctx=)``.  A failed replicate of a method whose objective is in ``zero_for`` gets zero metrics
     (run_method's rule); of any other raises NotPositiveDefinite "...: <what> after k steps".
-    Returns {method: {metric: array(TT), "theta"[, "Z" with m][, "failed" with zero_for]}}."""
+    Returns {method: {metric: array(TT), "theta"[, "Z" with m][, "failed" with zero_for]}}.
+    ``post`` (run_full_validated_batch): ``train`` also gets Xv= / yv=, the replicates' validation
+    rows, and post(entry, res, method, X, y, Xt, yt) adds to a method's entry."""
     from .gp import es_draws
     for name, meth in methods.items():
         if meth.objective not in accepts:
@@ -359,10 +364,12 @@ def _run_batch(who, sheets, TT, methods, accepts, why, route, train, what, m=Non
     Xt = np.stack([dd["test_x"] for dd in data])
     yt = np.stack([dd["test_y"] for dd in data])
     out = {}
+    va = {} if post is None else {"Xv": np.stack([dd["va_x"] for dd in data]),
+                                  "yv": np.stack([dd["va_y"] for dd in data])}
     for name, meth in methods.items():
         res = train(X, y, np.stack(th0[name]), np.stack(start[name]) if start[name] else None,
                     meth, lr=meth.lr, itr=steps[name], Xt=Xt, yt=yt, stale_noise=stale_noise,
-                    ctx=ctx)
+                    ctx=ctx, **va)
         failed = np.asarray(res.info) != 0
         if failed.any() and meth.objective not in zero_for:
             q = int(np.flatnonzero(failed)[0])
@@ -375,6 +382,8 @@ def _run_batch(who, sheets, TT, methods, accepts, why, route, train, what, m=Non
         out[name]["theta"] = res.theta.copy()
         if zero_for:
             out[name]["failed"] = failed
+        if post is not None:
+            post(out[name], res, meth, X, y, Xt, yt)
     return out
 
 
@@ -450,6 +459,59 @@ def run_full_blockloo_batch(sheets, TT=30, methods=None, itr=None, seed=None, re
                                                              nfold=nfold, **kw),
         "info {info} (the failing leading minor, or n + the fold block's row)", itr=itr, seed=seed,
         reseed=reseed, stale_noise=stale_noise, ctx=ctx)
+
+
+def run_full_validated_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
+                             stale_noise=True, va_every=1, select=None, ctx=None, nfold=4):
+    """run_full_batch / run_full_blockloo_batch with every replicate's validation split (va_x /
+    va_y, the 300 rows KF:203-209 holds out) scored inside the fits, step by step: the
+    series the scripts carry commented out and chose their step counts by.  Pointwise methods go
+    through ONE train_tall_validated call each, dss / kc through ONE blockloo_train_tall_validated
+    call; ``methods`` defaults to KF_METHODS' crps, nlml, logs and dss entries.  A method whose
+    objective is es raises ValueError: its route is run_full_es_batch, which has no validation.
+    Data replicates and starting points are drawn in run's order, so with the same ``seed`` this
+    fits the problems run_full_batch / run_full_blockloo_batch fit, and the standard entries —
+    {metric: array(TT), "theta"} — are theirs.  Added per method: "va_scores" {name: array(TT,
+    nva)} over SCORE_NAMES, "va_steps" (nva,), and with ``select`` (a metric of
+    batch.SELECT_METRICS) "best_step" array(TT) and "selected" {metric: array(TT)}: the test
+    metrics at each replicate's theta_best, from one more train_tall(itr=0, theta0=theta_best)
+    call for the batch; a replicate whose best row is the final one keeps the first call's
+    metrics (under stale_noise that row's noise is the stale one).  ``itr``, stale_noise and
+    failures as run_full_batch."""
+    from .batch import (_select_metric, _va_every, blockloo_train_tall_validated,
+                        train_tall_validated)
+    if methods is None:
+        methods = {k: KF_METHODS[k] for k in ("crps", "nlml", "logs", "dss")}
+    va_every, select = _va_every(va_every), _select_metric(select)
+
+    def train(X, y, th0, _, meth, **kw):
+        if meth.objective in BLOCK_BATCH_OBJS:
+            return blockloo_train_tall_validated(X, y, th0, objective=meth.objective, nfold=nfold,
+                                                 va_every=va_every, select=select, **kw)
+        return train_tall_validated(X, y, th0, objective=meth.objective, va_every=va_every,
+                                    select=select, **kw)
+
+    def post(entry, res, meth, X, y, Xt, yt):
+        entry["va_scores"] = {k: v.copy() for k, v in res.va_scores.items()}
+        entry["va_steps"] = res.va_steps.copy()
+        if select is None:
+            return
+        entry["best_step"] = res.best_step.copy()
+        sel = {k: np.array(entry[k], dtype=np.float64) for k in METRICS}
+        redo = np.flatnonzero(res.best_step != res.va_steps[-1])  # not the final row
+        if redo.size:
+            r2 = train_tall(X[redo], y[redo], res.theta_best[redo], itr=0, Xt=Xt[redo],
+                            yt=yt[redo], ctx=ctx)
+            for k in METRICS:
+                sel[k][redo] = r2.scores["test_" + k]
+        entry["selected"] = sel
+
+    return _run_batch(
+        "run_full_validated_batch", sheets, TT, methods, tuple(BATCH_OBJS) + tuple(BLOCK_BATCH_OBJS),
+        "which has no validated batch path (the energy-score route has no validation)",
+        lambda o: "run_full_es_batch" if o == "es" else "run(kind=\"full\")", train,
+        "info {info} (the failing leading minor, or n + the fold block's row)", itr=itr, seed=seed,
+        reseed=reseed, stale_noise=stale_noise, ctx=ctx, post=post)
 
 
 def run_full_es_batch(sheets, TT=30, methods=None, itr=None, seed=None, reseed=True,
