@@ -173,6 +173,12 @@ enum {
                              batches.  Default 2 | 2 << 4.  For a given option 29 the bits are those of
                              the strips (same K range and per-element product chain; DESIGN
                              §29). */
+  GPS_OPT_GEMM_LIVE = 31,   /* 1 (default): the 64/128-tile GEMM skips the MFMA blocks of an edge
+                             tile that lie wholly in the padding, where the caller knows the
+                             products to be exact zeros (rows >= n of the full GP's factorisation
+                             products and of the predictive product) or never read (its columns
+                             >= n*); 0: every block multiplied.  Same values bitwise for finite
+                             operands. */
 };
 int gps_ctx_set_option(gps_ctx* ctx, int key, int value);
 

@@ -185,6 +185,7 @@ int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t
   if (!st) st = ctx->stream;
   GemmParams q = p;
   if (q.map_mode == 0) q.map_mode = ctx->gemm_map;
+  if (!ctx->gemm_live) q.m_live = q.n_live = 0;  // GPS_OPT_GEMM_LIVE off: every block multiplied
   // the stream's slabs: gemm_plan may split K on small grids; an explicit 64-tile split uses them
   if (epi == EPI_STORE && (q.ksplit == 1 || q.tile == 64) && !q.ws) {
     DBuf& ws = st == ctx->side      ? ctx->ws_side
@@ -251,6 +252,10 @@ int pred_rows(gps_ctx* ctx, int64_t r0, int64_t r1, const double* w, hipStream_t
   p.out0 = ctx->pslab.d() + (r0 / GPS_TILE) * ntp;
   p.out1 = ctx->pslab.d() + (tiles_m + r0 / GPS_TILE) * ntp;
   p.ld_out = ntp;
+  // rows >= n of V are zeros (L⁻¹'s padding rows are identity rows and K_f*'s rows k >= n are the
+  // Gram's zero padding); columns >= n* are zeros too (K_f*'s padding columns) and never read
+  p.m_live = (int)std::min<int64_t>(std::max<int64_t>(pad_to(ctx->n, 16) - r0, 0), r1 - r0);
+  p.n_live = (int)pad_to(ctx->nt, 16);
   return gemm(ctx, LAY_N, LAY_T, EPI_COLRED, p, st);
 }
 
@@ -386,6 +391,11 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
   double* A22 = A21 + n1;
   double* Li21 = Linv + (int64_t)n1 * ldl;
   double* Li22 = Li21 + n1;
+  // live rows of the A22 side: the full GP's matrix is diag(A, I) written by the Gram kernel
+  // (pad_identity: zeros off the padded diagonal), so rows >= nreal of A21 are zeros, and with them
+  // those of every product below.  0: the whole extent, no hint — the other factorisations (FITC's
+  // B, the folds, the joint blocks), whose padding other kernels write, keep that
+  const int ml = ctx->dag_full ? std::min(n2, std::max(0, (int)pad_to(nreal - n1, 16))) : 0;
   int rc;
   // top level with a pre-pass request whose L11 block is one persistent launch and a signal block
   // (GPS_OPT_FITC_DEP, C5): the pre-pass's column tiles start beside that launch, each as soon as
@@ -421,6 +431,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     GemmParams p = gp0();
     p.A = A21; p.lda = lda; p.B = Linv; p.ldb = ldl; p.C = W; p.ldc = n1;
     p.M = n2; p.N = n1; p.K = n1; p.tri = TRI_K_LE_J;
+    p.m_live = ml;  // A21's padding rows are zeros, so W's are
     if ((rc = gemm(ctx, LAY_N, LAY_T, EPI_STORE, p))) return rc;
     ++ctx->fplan.gemms;
   }
@@ -441,6 +452,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     p.A = W; p.lda = n1; p.B = W; p.ldb = n1; p.C = A22; p.ldc = lda;
     p.M = n2; p.N = n2; p.K = n1; p.alpha = -1.0; p.beta = 1.0; p.lower_out = 1;
     p.sk_alone = forked ? 0 : 1;
+    p.m_live = p.n_live = ml;  // W's padding rows are zeros on both sides; beta·C keeps A22's identity
     if ((rc = gemm(ctx, LAY_N, LAY_T, EPI_STORE, p))) return rc;
     ++ctx->fplan.gemms;
   }
@@ -448,6 +460,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     GemmParams p = gp0();
     p.A = W; p.lda = n1; p.B = Linv; p.ldb = ldl; p.C = A21; p.ldc = lda;
     p.M = n2; p.N = n1; p.K = n1; p.tri = TRI_K_GE_J;
+    p.m_live = ml;  // W's padding rows are zeros, so T's are
     if ((rc = gemm(ctx, LAY_N, LAY_N, EPI_STORE, p, ts))) return rc;
     ++ctx->fplan.gemms;
   }
@@ -478,6 +491,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     GemmParams p = gp0();
     p.A = Li22; p.lda = ldl; p.B = A21; p.ldb = lda; p.C = Li21; p.ldc = ldl;
     p.M = n2; p.N = n1; p.K = n2; p.alpha = -1.0; p.tri = TRI_K_LE_I;
+    p.m_live = ml;  // L22⁻¹'s padding rows are identity rows, not zeros: they pick T's zero rows
     if ((rc = gemm(ctx, LAY_N, LAY_N, EPI_STORE, p))) return rc;
     ++ctx->fplan.gemms;
   }
@@ -576,7 +590,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
   std::vector<uintptr_t> key = {
       (uintptr_t)A, (uintptr_t)n_pad, (uintptr_t)Linv, (uintptr_t)W, (uintptr_t)logdiag,
       (uintptr_t)nreal, (uintptr_t)Lout, (uintptr_t)ctx->stream, (uintptr_t)ctx->side,
-      (uintptr_t)ctx->overlap, (uintptr_t)ctx->gemm_map,
+      (uintptr_t)ctx->overlap, (uintptr_t)ctx->gemm_map, (uintptr_t)ctx->gemm_live, (uintptr_t)ctx->dag_full,
       (uintptr_t)g_tiny_gemm, (uintptr_t)g_stream_k, (uintptr_t)g_slab_xcd, (uintptr_t)ctx->info.p, (uintptr_t)ctx->ws_main.p,
       (uintptr_t)ctx->ws_side.p, (uintptr_t)pre,
       // the pre-pass's operands (only when it is part of the sequence)
@@ -859,6 +873,7 @@ int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
              "GPS_OPT_DAG_KBATCH must be B | g << 4 [| 256] with B in 0..8 and g in 0..3");
       ctx->dag_kbatch = (value & 15) < 2 ? 0 : value;
       return 0;
+    case GPS_OPT_GEMM_LIVE: ctx->gemm_live = value != 0; return 0;
     case GPS_OPT_DAG_TILE_FORM:
       ARGCHK(value >= 0 && (value & 15) <= 8 && (value >> 8) == 0 && ((value & 15) || !value),
              "GPS_OPT_DAG_TILE_FORM must be 0 or minlen | d << 4 with minlen in 1..8 and d in 0..15");

@@ -58,6 +58,12 @@ static bool diag_check(const gps_gemm_desc& d, bool have_c, bool have_kscale, bo
                "kr entries must be multiples of 16 in [0, K]");
   }
   DIAG_REQ(d.kend >= 0 && d.kend % 16 == 0, "kend must be 0 or a positive multiple of 16");
+  // the live-extent hints: dead_m16 | dead_n16 << 8 trailing dead 16-blocks of M and N
+  DIAG_REQ(d.reserved >= 0 && (d.reserved >> 16) == 0 && (d.reserved & 128) == 0 &&
+               (d.reserved >> 8 & 128) == 0,
+           "reserved must be dead_m16 | dead_n16 << 8 with both in 0..127");
+  DIAG_REQ((d.reserved & 127) <= d.M / 16 && (d.reserved >> 8 & 127) <= d.N / 16,
+           "reserved: more dead 16-blocks than M/16 or N/16");
   DIAG_REQ((d.lower_out == 0 || d.lower_out == 1) && (d.mirror == 0 || d.mirror == 1),
            "lower_out and mirror are flags");
   DIAG_REQ(!d.lower_out || d.M == d.N, "lower_out needs a square output");
@@ -131,6 +137,9 @@ static GemmParams desc_params(const gps_gemm_desc& d) {
   p.lower_out = d.lower_out; p.ksplit = d.ksplit; p.tri = d.tri; p.tri_off = d.tri_off;
   p.map_mode = d.map_mode; p.tile = d.tile; p.mirror = d.mirror; p.kend = d.kend;
   p.sk_alone = d.sk_alone;
+  // (all dead gives 0, the whole extent: nothing is skipped then)
+  if (d.reserved & 127) p.m_live = d.M - 16 * (d.reserved & 127);
+  if (d.reserved >> 8 & 127) p.n_live = d.N - 16 * (d.reserved >> 8 & 127);
   return p;
 }
 // a slabbed 128-tile split names its slabs itself (gemm() hands the stream's workspace only to

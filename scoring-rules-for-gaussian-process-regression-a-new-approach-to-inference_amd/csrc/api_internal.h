@@ -138,6 +138,7 @@ struct gps_ctx {
                                        // task; 256: in blocks above dag_tiles only)
   int dag_tile_form = 2 | 2 << 4;      // GPS_OPT_DAG_TILE_FORM: minlen | d << 4 (0: strips only)
   bool dag_full = false;               // this factorisation is full_fit_core's (dag_tiles_full applies)
+  bool gemm_live = true;               // GPS_OPT_GEMM_LIVE: the GEMMs' live-extent hints (gemm())
   bool dag_half = false;               // this factorisation leaves half the CUs to a side stream
   bool fitc_dep = true;                // GPS_OPT_FITC_DEP: the q row norms behind Lm's factorisation
   int* dag_sig = nullptr;              // the top-level persistent launch's row signals (kSig*), if any

@@ -85,6 +85,12 @@ struct GemmParams {
                              // pairs dealt slice-major in contiguous runs per XCD
   int kend;                  // > 0 (a multiple of 16): A's columns k >= kend are zero (the FITC row
                              // norms: kend = m rounded to 16) — the K loop stops there
+  int m_live, n_live;        // > 0 (multiples of 16): the caller's promise that output rows >=
+                             // m_live are exact zeros before alpha/beta, resp. that output columns
+                             // >= n_live are exact zeros there or never read (padding rows /
+                             // columns whose operand rows are zero) — a 64/128-tile that crosses
+                             // the extent skips the MFMA blocks beyond it (gemm_tile's edge loop;
+                             // GPS_OPT_GEMM_LIVE).  0: the whole extent
   int sk_alone;              // the launch runs without a concurrent forked product (potrf_inv_rec's
                              // trailing update when nothing is forked beside it): the stream-K
                              // tail fills its last round (GPS_OPT_STREAM_K = 2, the default)

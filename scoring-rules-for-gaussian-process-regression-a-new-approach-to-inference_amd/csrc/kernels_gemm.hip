@@ -142,12 +142,12 @@ __device__ bool dep_take(const GemmParams& p, double* smem, int& ti, int& tj) {
   return true;
 }
 
-template <int ALAY, int BLAY, int EPI, int TILE>
+template <int ALAY, int BLAY, int EPI, int TILE, bool EDGE = true>
 __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, int kslice,
                                           double* smem, int kb_o = -1, int ke_o = -1,
                                           double* part = nullptr);
 template <int ALAY, int BLAY>
-__device__ void gemm_sk_block(const GemmParams& p, int s, double* smem);
+__device__ __forceinline__ void gemm_sk_block(const GemmParams& p, int s, double* smem);
 
 template <int ALAY, int BLAY, int EPI, int TILE>
 __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmParams p) {
@@ -232,7 +232,7 @@ __device__ __forceinline__ void store_acc(const GemmParams& p, int ti, int tj, i
 // reproducible (cdna_hip_programming.md §5 "In-launch split-K reduction", plain-store recipe).
 // The last arriver also zeroes the tile's ticket for the next launch.
 template <int ALAY, int BLAY>
-__device__ void gemm_sk_block(const GemmParams& p, int s, double* smem) {
+__device__ __forceinline__ void gemm_sk_block(const GemmParams& p, int s, double* smem) {
   constexpr int TILE = 128, MI = TILE / 32, TT = TILE * TILE;
   const int tiles = p.lower_out ? p.tiles_m * (p.tiles_m + 1) / 2 : p.tiles_m * p.tiles_n;
   const int nk = p.K / BK;
@@ -248,10 +248,10 @@ __device__ void gemm_sk_block(const GemmParams& p, int s, double* smem) {
     tile_of(p, p.sk_dp + u, ti, tj);
     const int s0 = part.owner((int64_t)u * nk), s1 = part.owner((int64_t)u * nk + nk - 1);
     if (s0 == s1) {  // the whole tile in this run
-      gemm_tile<ALAY, BLAY, EPI_STORE, TILE>(p, ti, tj, 0, smem);
+      gemm_tile<ALAY, BLAY, EPI_STORE, TILE, false>(p, ti, tj, 0, smem);
       __syncthreads();  // (its last slice is still being read when the next run stages)
     } else {
-      gemm_tile<ALAY, BLAY, EPI_STORE, TILE>(p, ti, tj, 0, smem, k0 * BK, k1 * BK,
+      gemm_tile<ALAY, BLAY, EPI_STORE, TILE, false>(p, ti, tj, 0, smem, k0 * BK, k1 * BK,
                                              p.ws + (int64_t)(u + s) * TT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -293,7 +293,7 @@ __device__ void gemm_sk_block(const GemmParams& p, int s, double* smem) {
   }
 }
 
-template <int ALAY, int BLAY, int EPI, int TILE>
+template <int ALAY, int BLAY, int EPI, int TILE, bool EDGE>
 __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, int kslice,
                                           double* smem, int kb_o, int ke_o, double* part) {
   constexpr int LS = TILE + 16;          // LDS row stride (doubles)
@@ -424,6 +424,55 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
     }
   };
 
+  // Live extents (GemmParams::m_live / n_live): a tile that crosses one runs the edge
+  // copy of the loop below, whose compute issues the MFMAs of this wave's live 16-blocks only
+  // (mi < mi_n, ni < ni_n: wave-uniform, in scalars; a wave with nothing live reads no fragment
+  // either).  Decided once per tile, uniformly for the workgroup; a tile inside the extents takes
+  // the full loop untouched.  The store and column-reduction kernels only: launch_gemm clears the
+  // fields for the row-norm epilogues, which no caller hints and whose registers are at the limit.
+  // Bits: a skipped block's operand rows (columns) are zeros by the caller's promise, and from +0,
+  // fma(0, b, +0) = +0 for every finite b — the skipped accumulators hold exactly what the full
+  // loop leaves, so every stored value is bitwise the full loop's.  The one exception is a
+  // non-finite factor opposite the zeros (0·∞, 0·NaN), which only a failed factorisation
+  // produces and check_info discards anyway (as §29 states for its clipped term).  Skipped
+  // columns that are merely never read (n_live) differ where the full loop had non-zeros.
+  constexpr bool LIVE = EDGE && (EPI == EPI_STORE || EPI == EPI_COLRED);
+  const int mrem = LIVE && p.m_live > 0 ? p.m_live - row0 : TILE;  // live rows / columns of this tile
+  const int nrem = LIVE && p.n_live > 0 ? p.n_live - col0 : TILE;
+  const bool edge = mrem < TILE || nrem < TILE;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  const int mi_n = min(MI, max(0, (mrem - (wv >> 1) * WT) >> 4));
+  const int ni_n = min(MI, max(0, (nrem - (wv & 1) * WT) >> 4));
+  auto compute_edge = [&](int buf) {
+    if (mi_n == 0 || ni_n == 0) return;
+    const double* As = smem + buf * STAGE;
+    const double* Bs = As + BK * LS;
+    auto frags = [&](int kk, double (&fa)[MI], double (&fb)[MI]) {
+      const int krow = rowoff(kk * 4 + (lane >> 4)) + (lane & 15);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) fa[mi] = As[krow + wr * WT + mi * 16];
+#pragma unroll
+      for (int ni = 0; ni < MI; ++ni) fb[ni] = Bs[krow + wc * WT + ni * 16];
+    };
+    // A rolled kk loop: unrolled, the compiler gathers the four steps of each block under one
+    // test and keeps all their fragments live at once (64 more VGPRs, spilled).  Reading the next
+    // step's fragments ahead cost the column-reduction kernel 9 VGPRs over the parent's and is
+    // left out.
+#pragma unroll 1
+    for (int kk = 0; kk < BK / 4; ++kk) {
+      double a[MI], b[MI];
+      frags(kk, a, b);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+        if (mi < mi_n) {
+#pragma unroll
+          for (int ni = 0; ni < MI; ++ni)
+            if (ni < ni_n)
+              acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+        }
+    }
+  };
+
   // EPI_ROWSQ_DOT: the last column tile spans the full K range, so its A rows also give
   // A[row,:]·w — threads 0..TILE-1 take one row each from the slice image in LDS (w read
   // wave-uniform), which spares the caller a separate pass over A (FITC g = Knm c)
@@ -445,17 +494,23 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
     __syncthreads();
     // steady state: prefetch slice it+1 into registers, multiply slice it, then
     // park the prefetched slice in the other LDS buffer (no branches in the body)
-    for (int it = 0; it < nk - 1; ++it) {
-      load_tile(kb + (it + 1) * BK);
-      if (p.prio) __builtin_amdgcn_s_setprio(1);
-      compute(it & 1);
-      if (p.prio) __builtin_amdgcn_s_setprio(0);
-      row_dot(it & 1, kb + it * BK);
-      store_tile((it + 1) & 1);
-      __syncthreads();
-    }
-    compute((nk - 1) & 1);
-    row_dot((nk - 1) & 1, kb + (nk - 1) * BK);
+    auto mainloop = [&](auto& mma) {
+      for (int it = 0; it < nk - 1; ++it) {
+        load_tile(kb + (it + 1) * BK);
+        if (p.prio) __builtin_amdgcn_s_setprio(1);
+        mma(it & 1);
+        if (p.prio) __builtin_amdgcn_s_setprio(0);
+        row_dot(it & 1, kb + it * BK);
+        store_tile((it + 1) & 1);
+        __syncthreads();
+      }
+      mma((nk - 1) & 1);
+      row_dot((nk - 1) & 1, kb + (nk - 1) * BK);
+    };
+    // the edge copy: same staging, barriers and double buffer (a wave with nothing live still
+    // reaches every barrier), live blocks only in its compute
+    if (!edge) mainloop(compute);
+    else mainloop(compute_edge);
   }
   if constexpr (EPI == EPI_ROWSQ_DOT) {
     if (rdot && tid < TILE) p.out1[row0 + tid] = dacc;
@@ -782,6 +837,14 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
   if (p.lower_out && p.M != p.N) return hipErrorInvalidValue;
   if (p.mirror && (!p.lower_out || p.M % 32)) return hipErrorInvalidValue;
   if (p.ksplit < 1) p.ksplit = 1;
+  // live extents: multiples of 16 inside the output; the whole extent is 0 (gemm_tile's full loop)
+  if (p.m_live < 0 || p.m_live > p.M || (p.m_live & 15) || p.n_live < 0 || p.n_live > p.N ||
+      (p.n_live & 15))
+    return hipErrorInvalidValue;
+  if (p.m_live == p.M) p.m_live = 0;
+  if (p.n_live == p.N) p.n_live = 0;
+  // (the small kernel and the row-norm epilogues have no edge loop)
+  if (p.dep_mode || epi == EPI_ROWSQ || epi == EPI_ROWSQ_DOT) p.m_live = p.n_live = 0;
   // the row dot comes from the last column tile, which must span the whole K range (columns
   // [tri_off, tri_off + N) of a larger triangular product whose last column is K)
   if (epi == EPI_ROWSQ_DOT &&
@@ -792,6 +855,7 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
   const int tile = plan.tile;
   if (tile == 16 || tile == 32) {  // small kernel: tile = block edge, ksplit = waves per block
     if (epi != EPI_STORE || p.kscale) return hipErrorInvalidValue;
+    p.m_live = p.n_live = 0;
     const int wpt = plan.ksplit;
     if (wpt != 1 && wpt != 2 && wpt != 4) return hipErrorInvalidValue;
     const int64_t tt = small_tiles(p, tile);

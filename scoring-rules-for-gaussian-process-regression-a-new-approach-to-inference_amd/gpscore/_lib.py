@@ -35,6 +35,7 @@ GPS_OPT_FITC_DEP = 27
 GPS_OPT_DAG_TILES_FULL = 28
 GPS_OPT_DAG_KBATCH = 29
 GPS_OPT_DAG_TILE_FORM = 30
+GPS_OPT_GEMM_LIVE = 31  # 1 (default): edge tiles skip the MFMA blocks that lie in the padding
 # the library's defaults of those two (api_internal.h): 40-tile blocks in the full GP's fit, and
 # batches of 8 K tiles in the blocks above GPS_OPT_DAG_TILES (bit 8 of the batch option)
 DAG_TILES_FULL_DEFAULT = 40
