@@ -135,6 +135,17 @@ hipEvent_t sync_event(gps_ctx* c) {
   }
   return c->sync_ev[c->sync_used++];
 }
+hipEvent_t own_event(hipEvent_t& e) {  // ... or one of the context's own, created on first use
+  if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr;
+  return e;
+}
+// fork: the stream `to` waits for the work `from` holds so far
+int fork_to(gps_ctx* ctx, hipEvent_t e, hipStream_t from, hipStream_t to) {
+  if (!e) return fail(ctx, -2, "hipEventCreate failed");
+  HIPCHK(hipEventRecord(e, from));
+  HIPCHK(hipStreamWaitEvent(to, e, 0));
+  return 0;
+}
 
 // --------------------------------------------------------------- launch helpers
 
@@ -184,8 +195,8 @@ int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t
          GemmLaunchInfo* info) {
   if (!st) st = ctx->stream;
   GemmParams q = p;
-  if (q.map_mode == 0) q.map_mode = ctx->gemm_map;
-  if (!ctx->gemm_live) q.m_live = q.n_live = 0;  // GPS_OPT_GEMM_LIVE off: every block multiplied
+  if (q.map_mode == 0) q.map_mode = ctx->fo.gemm_map;
+  if (!ctx->fo.gemm_live) q.m_live = q.n_live = 0;  // GPS_OPT_GEMM_LIVE off: every block multiplied
   // the stream's slabs: gemm_plan may split K on small grids; an explicit 64-tile split uses them
   if (epi == EPI_STORE && (q.ksplit == 1 || q.tile == 64) && !q.ws) {
     DBuf& ws = st == ctx->side      ? ctx->ws_side
@@ -292,41 +303,41 @@ int fitc_rowsq_dep(gps_ctx* ctx, const double* L, int* sig, int64_t ncols, int m
   return gemm(ctx, LAY_N, LAY_T, EPI_ROWSQ, p, st);
 }
 
-// the task list of an nb-tile persistent block under the context's options
-int dag_list_key(const gps_ctx* ctx, int64_t nb) {  // 8 + 2 + 4 + 8 bits
-  return ((int)(3 * nb + ctx->dag_order) << 8 | dag_kg(ctx, nb) << 4 | dag_kb(ctx, nb)) << 8 | dag_tf(ctx, nb);
-}
 // the K batches of an nb-tile block's task list (GPS_OPT_DAG_KBATCH): at most B terms, the last g
 // single; with bit 8 set only in blocks above GPS_OPT_DAG_TILES — smaller ones are bound by
 // their leaf chain, which batches of 8 only delay (2560 columns: 1.05 -> 1.15 ms)
-int dag_kb(const gps_ctx* ctx, int64_t nb) {
-  if ((ctx->dag_kbatch & 256) && nb <= ctx->dag_tiles) return 1;
-  return std::max(1, ctx->dag_kbatch & 15);
+static int dag_kb(const gps_ctx* ctx, int64_t nb) {
+  if ((ctx->fo.dag_kbatch & 256) && nb <= ctx->fo.dag_tiles) return 1;
+  return std::max(1, ctx->fo.dag_kbatch & 15);
 }
-int dag_kg(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->dag_kbatch >> 4 & 3 : 0; }
+static int dag_kg(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->fo.dag_kbatch >> 4 & 3 : 0; }
 // the batches of an nb-tile block that run in tile form (GPS_OPT_DAG_TILE_FORM): only where there
 // are batches — the single-term lists (the FITC blocks, every block up to GPS_OPT_DAG_TILES under
 // the default) stay word for word what they were
-int dag_tf(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->dag_tile_form : 0; }
+static int dag_tf(const gps_ctx* ctx, int64_t nb) { return dag_kb(ctx, nb) > 1 ? ctx->fo.dag_tile_form : 0; }
+// the task list of an nb-tile persistent block under the context's options
+static int dag_list_key(const gps_ctx* ctx, int64_t nb) {  // 8 + 2 + 4 + 8 bits
+  return ((int)(3 * nb + ctx->dag_order) << 8 | dag_kg(ctx, nb) << 4 | dag_kb(ctx, nb)) << 8 | dag_tf(ctx, nb);
+}
 
 // a block of nb 128-tiles goes to the persistent factorisation (GPS_OPT_DAG); the full GP's
-// factorisation has a cap of its own (GPS_OPT_DAG_TILES_FULL)
-bool dag_block(const gps_ctx* ctx, int64_t nb) {
-  const int cap = ctx->dag_full && ctx->dag_tiles_full ? ctx->dag_tiles_full : ctx->dag_tiles;
-  return ctx->dag && nb >= 2 && nb <= cap;
+// factorisation (full: FactorReq::full) has a cap of its own (GPS_OPT_DAG_TILES_FULL)
+bool dag_block(const gps_ctx* ctx, int64_t nb, bool full) {
+  const int cap = full && ctx->fo.dag_tiles_full ? ctx->fo.dag_tiles_full : ctx->fo.dag_tiles;
+  return ctx->fo.dag && nb >= 2 && nb <= cap;
 }
 
 // the block sizes the recursion of an nb-tile factorisation hands to the persistent kernel, and
 // how many counter ints all of them need together
-void dag_blocks(const gps_ctx* ctx, int64_t nb, std::vector<int>& sizes, int64_t& cnt) {
+static void dag_blocks(const gps_ctx* ctx, int64_t nb, bool full, std::vector<int>& sizes, int64_t& cnt) {
   if (nb <= 1) return;
-  if (dag_block(ctx, nb)) {
+  if (dag_block(ctx, nb, full)) {
     sizes.push_back((int)nb);
     cnt += dag_cnt_ints((int)nb);
     return;
   }
-  dag_blocks(ctx, nb / 2, sizes, cnt);
-  dag_blocks(ctx, nb - nb / 2, sizes, cnt);
+  dag_blocks(ctx, nb / 2, full, sizes, cnt);
+  dag_blocks(ctx, nb - nb / 2, full, sizes, cnt);
 }
 
 // workgroups of a persistent launch of nb tiles: one per CU, or half the CUs for the FITC m×m
@@ -337,7 +348,7 @@ void dag_blocks(const gps_ctx* ctx, int64_t nb, std::vector<int>& sizes, int64_t
 // measured 11.71 / 11.73 against 11.56 ms (profiles/r6i_fitc_dep_ab_c4_phases.txt)
 int dag_width(const gps_ctx* ctx, int64_t nb, bool half) {
   const int auto_w = half ? std::max(4, ctx->ncu / 2) : ctx->ncu;
-  return (int)std::min<int64_t>(ctx->dag_wgs > 0 ? ctx->dag_wgs : auto_w, std::max<int64_t>(4, 2 * nb * nb));
+  return (int)std::min<int64_t>(ctx->fo.dag_wgs > 0 ? ctx->fo.dag_wgs : auto_w, std::max<int64_t>(4, 2 * nb * nb));
 }
 
 // recursive Cholesky + inverse on a padded (multiple of 128) SPD block.
@@ -345,22 +356,26 @@ int dag_width(const gps_ctx* ctx, int64_t nb, bool half) {
 // the region after it, so a concurrent GEMM that still reads this level's W never
 // races with them.
 //
-// T = L21 L11⁻¹ only feeds the final L⁻¹21 product, so (ctx->overlap) it runs on the
+// T = L21 L11⁻¹ only feeds the final L⁻¹21 product, so (ctx->fo.overlap) it runs on the
 // side stream (fork / join events) concurrently with the trailing update and rec(A22).
 // Measured on C3 and dropped from the build (round 1): a lookahead split of the trailing
 // update, CU-masked side streams and split-K fill of the top-level SYRK — each neutral or
 // slower end to end, because the side stream's T product already fills the idle slots.
-int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ldl, double* W,
-                  int nb, double* logdiag, int* info, int base, int nreal, double* Lout,
-                  int64_t ldlo, bool top) {
+// sig: the row signals this block's launch carries — the top call's req.sig, rec(A11)'s req.pre.sig
+// under a dependent pre-pass, null everywhere else; the block then must be one persistent launch.
+static int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ldl, double* W,
+                         int nb, double* logdiag, int* info, int base, int nreal, double* Lout,
+                         int64_t ldlo, const FactorReq& req, bool top, int* sig) {
   hipStream_t s = ctx->stream;
+  if (sig && !dag_block(ctx, nb, req.full))
+    return fail(ctx, -1, "potrf_inv: row signals for a block of several launches (internal contract)");
   if (nb == 1) {
     Prof pr(ctx, "potrf_diag128", 2.0 * 128 * 128 * 128 / 3.0, 0);
     HIPCHK(launch_potrf_leaf(A, lda, Linv, ldl, Lout, ldlo, logdiag, info, base, nreal, s));
     ++ctx->fplan.leaves;
     return 0;
   }
-  if (dag_block(ctx, nb)) {  // the whole block in one persistent launch (kernels_potrf.hip)
+  if (dag_block(ctx, nb, req.full)) {  // the whole block in one persistent launch (kernels_potrf.hip)
     auto it = ctx->dag_lists.find(dag_list_key(ctx, nb));
     const int64_t need = dag_cnt_ints(nb);
     if (it == ctx->dag_lists.end() || ctx->dag_cnt_used + need > (int64_t)(ctx->dag_cnt.cap / 4))
@@ -371,14 +386,13 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     d.tasks = static_cast<const uint32_t*>(it->second.first.p); d.ntasks = it->second.second;
     d.cnt = static_cast<int*>(ctx->dag_cnt.p) + ctx->dag_cnt_used;
     d.spin_ticks = 200000000ull;  // 2 s at the 100 MHz real-time clock
-    d.group = ctx->dag_group;
+    d.group = ctx->fo.dag_group;
     d.kbatch = dag_kb(ctx, nb);
-    d.sig = ctx->dag_sig;  // (a dependent row-norm launch reads its rows: the first block only)
-    ctx->dag_sig = nullptr;
+    d.sig = sig;  // (a dependent row-norm launch reads its rows)
     ctx->dag_cnt_used += need;
     const double nn = 128.0 * nb;
     Prof pr(ctx, "potrf_dag", 2.0 * nn * nn * nn / 3.0, 0);
-    HIPCHK(launch_potrf_dag(d, dag_width(ctx, nb, ctx->dag_half), s));
+    HIPCHK(launch_potrf_dag(d, dag_width(ctx, nb, req.half), s));
     gps_ctx::FactorPlan& fp = ctx->fplan;
     fp.dag_tmin = fp.dags ? std::min(fp.dag_tmin, nb) : nb;
     fp.dag_tmax = std::max(fp.dag_tmax, nb);
@@ -395,13 +409,14 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
   // (pad_identity: zeros off the padded diagonal), so rows >= nreal of A21 are zeros, and with them
   // those of every product below.  0: the whole extent, no hint — the other factorisations (FITC's
   // B, the folds, the joint blocks), whose padding other kernels write, keep that
-  const int ml = ctx->dag_full ? std::min(n2, std::max(0, (int)pad_to(nreal - n1, 16))) : 0;
+  const int ml = req.full ? std::min(n2, std::max(0, (int)pad_to(nreal - n1, 16))) : 0;
   int rc;
   // top level with a pre-pass request whose L11 block is one persistent launch and a signal block
   // (GPS_OPT_FITC_DEP, C5): the pre-pass's column tiles start beside that launch, each as soon as
   // its row of L11⁻¹ is final, and a completion launch takes the rest once L11⁻¹ is (below)
-  const bool pre_here = top && ctx->pre.kind == PRE_FITC_Q && ctx->pre.n1 == n1;
-  const bool pre_dep = pre_here && ctx->pre.sig && ctx->overlap && dag_block(ctx, n1b);
+  const bool pre_here = top && req.pre.kind == PRE_FITC_Q && req.pre.n1 == n1;
+  const bool pre_dep = pre_here && req.pre.sig && ctx->fo.overlap && dag_block(ctx, n1b, req.full);
+  hipEvent_t pre_join = nullptr;  // the pre-pass's stream joins before this frame returns
   // (on aux[1]: aux[0] may still hold the test-side pre-pass, FIFO ahead of it)
   // (an error return after the fork joins aux[1] first: no launch of this call may still run
   //  beside the context's next one)
@@ -411,18 +426,14 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     if (j && hipEventRecord(j, ctx->aux[1]) == hipSuccess) (void)hipStreamWaitEvent(s, j, 0);
   };
   if (pre_dep) {
-    hipEvent_t f = sync_event(ctx);
-    if (!f) return fail(ctx, -2, "hipEventCreate failed");
-    HIPCHK(hipEventRecord(f, s));
-    HIPCHK(hipStreamWaitEvent(ctx->aux[1], f, 0));
-    if ((rc = fitc_rowsq_dep(ctx, Linv, ctx->pre.sig, n1, 1, ctx->aux[1], n1b))) {
+    if ((rc = fork_to(ctx, sync_event(ctx), s, ctx->aux[1]))) return rc;
+    if ((rc = fitc_rowsq_dep(ctx, Linv, req.pre.sig, n1, 1, ctx->aux[1], n1b))) {
       join_dep();
       return rc;
     }
-    ctx->dag_sig = ctx->pre.sig;  // (consumed by rec(A11)'s persistent launch)
   }
-  rc = potrf_inv_rec(ctx, A, lda, Linv, ldl, W, n1b, logdiag, info, base, nreal, Lout, ldlo);
-  ctx->dag_sig = nullptr;
+  rc = potrf_inv_rec(ctx, A, lda, Linv, ldl, W, n1b, logdiag, info, base, nreal, Lout, ldlo, req,
+                     false, pre_dep ? req.pre.sig : nullptr);
   if (rc) {
     join_dep();
     return rc;
@@ -438,14 +449,11 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
   if (Lout) HIPCHK(hipMemcpy2DAsync(Lout + (int64_t)n1 * ldlo, ldlo * 8, W, (size_t)n1 * 8,
                                     (size_t)n1 * 8, n2, hipMemcpyDeviceToDevice, s));
   // an event fork + join costs ~13 us of dependent-chain latency (tools/launch_latency.hip)
-  const bool forked = ctx->overlap;
+  const bool forked = ctx->fo.overlap;
   hipStream_t ts = forked ? ctx->side : s;
-  hipEvent_t fork = sync_event(ctx), join = sync_event(ctx);
-  if (!fork || !join) return fail(ctx, -2, "hipEventCreate failed");
-  if (forked) {
-    HIPCHK(hipEventRecord(fork, s));
-    HIPCHK(hipStreamWaitEvent(ts, fork, 0));
-  }
+  hipEvent_t join = sync_event(ctx);
+  if (!join) return fail(ctx, -2, "hipEventCreate failed");
+  if (forked && (rc = fork_to(ctx, sync_event(ctx), s, ts))) return rc;
   {  // trailing update A22 -= L21 L21ᵀ (lower tiles); alone (nothing forked) it takes the
      // stream-K tail for its last round of workgroup slots
     GemmParams p = gp0();
@@ -469,22 +477,19 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
   // rows (FITC: the q column tiles [0, n1)) runs on aux[0] while rec(A22) — mostly
   // latency-bound launches at m ≤ 4k — runs
   if (pre_here) {
-    hipStream_t ps = !ctx->overlap ? s : pre_dep ? ctx->aux[1] : ctx->aux[0];
+    hipStream_t ps = !ctx->fo.overlap ? s : pre_dep ? ctx->aux[1] : ctx->aux[0];
     if (ps != s) {
-      hipEvent_t f = sync_event(ctx);
-      ctx->pre.join = sync_event(ctx);
-      if (!f || !ctx->pre.join) return fail(ctx, -2, "hipEventCreate failed");
-      HIPCHK(hipEventRecord(f, s));
-      HIPCHK(hipStreamWaitEvent(ps, f, 0));
+      if (!(pre_join = sync_event(ctx))) return fail(ctx, -2, "hipEventCreate failed");
+      if ((rc = fork_to(ctx, sync_event(ctx), s, ps))) return rc;
     }
-    if ((rc = pre_dep ? fitc_rowsq_dep(ctx, Linv, ctx->pre.sig, n1, 2, ps, n1b)
+    if ((rc = pre_dep ? fitc_rowsq_dep(ctx, Linv, req.pre.sig, n1, 2, ps, n1b)
                       : fitc_rowsq_cols(ctx, Linv, 0, n1, ps)))
       return rc;
-    if (ps != s) HIPCHK(hipEventRecord(ctx->pre.join, ps));
+    if (ps != s) HIPCHK(hipEventRecord(pre_join, ps));
   }
   if ((rc = potrf_inv_rec(ctx, A22, lda, Li22, ldl, W + (int64_t)n1 * n2, n2b, logdiag + n1, info,
                           base + n1, nreal - n1, Lout ? Lout + (int64_t)n1 * ldlo + n1 : nullptr,
-                          ldlo)))
+                          ldlo, req, false, nullptr)))
     return rc;
   if (forked) HIPCHK(hipStreamWaitEvent(s, join, 0));
   {  // L⁻¹21 = −L22⁻¹ · T
@@ -495,10 +500,7 @@ int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ld
     if ((rc = gemm(ctx, LAY_N, LAY_N, EPI_STORE, p))) return rc;
     ++ctx->fplan.gemms;
   }
-  if (top && ctx->pre.join) {
-    HIPCHK(hipStreamWaitEvent(s, ctx->pre.join, 0));
-    ctx->pre.join = nullptr;
-  }
+  if (pre_join) HIPCHK(hipStreamWaitEvent(s, pre_join, 0));
   return 0;
 }
 
@@ -513,10 +515,6 @@ size_t potrf_ws_doubles(int64_t n_pad) {
   return (size_t)std::max<int64_t>(tot, GPS_TILE * GPS_TILE);
 }
 
-// factor the padded SPD matrix in A (destroyed) into Linv, logdiag (n_pad).  Linv (and Lout)
-// must hold zeros above the diagonal already — every caller memsets the buffer when it allocates
-// or resizes it; the factorisation writes the lower triangle only, the diagonal 16×16 tiles of
-// the leaves included.  Returns 0 or the LAPACK-style info (> 0).
 int reset_info(gps_ctx* ctx) {  // [first non-PD minor, persistent-kernel error]
   HIPCHK(hipMemsetAsync(ctx->info.p, 0x7f, 2 * sizeof(int), ctx->stream));
   return 0;
@@ -539,10 +537,46 @@ bool factor_zeroed(const gps_ctx* ctx, const double* p, int64_t n_pad) {
   return it != ctx->zeroed.end() && it->second == n_pad;
 }
 
+// The graph-cache key of one potrf_inv call, everything its captured sequence depends on: the
+// call's buffers and sizes (key, as passed in), the context's streams and scratch, FactorOpts and
+// the request, each whole, and the block sizes' task lists (GPS_OPT_DAG_ORDER acts through these).
+// Two normalisations let states the sequence cannot tell apart share a graph: the full GP's block
+// cap counts only under req.full, the pre-pass's operands (the request's and the context's) only
+// under a pre-pass.  (drop_graphs_in looks for buffer addresses among the words.)
+static std::vector<uintptr_t> factor_key(gps_ctx* ctx, const FactorReq& req,
+                                         std::vector<uintptr_t> key, const std::vector<int>& dsizes) {
+  FactorOpts fo = ctx->fo;
+  fo.tiny_gemm = g_tiny_gemm; fo.stream_k = g_stream_k; fo.slab_xcd = g_slab_xcd;
+  if (!req.full) fo.dag_tiles_full = 0;
+  FactorReq r = req;
+  const bool pre = r.pre.kind != PRE_NONE;
+  if (!pre) r.pre = FactorReq::Pre{};
+  for (const void* p : {(void*)ctx->stream, (void*)ctx->side, ctx->info.p, ctx->ws_main.p,
+                        ctx->ws_side.p, ctx->dag_cnt.p, ctx->sk_cnt.p})
+    key.push_back((uintptr_t)p);
+  for (uintptr_t v : {(uintptr_t)ctx->aux[0], (uintptr_t)ctx->Knm.p, (uintptr_t)ctx->fslab.p,
+                      (uintptr_t)ctx->fn_pad, (uintptr_t)ctx->m_pad})
+    key.push_back(pre ? v : 0);
+  auto whole = [&key](const void* v, size_t bytes) {  // a padding-free struct as zero-filled words
+    key.resize(key.size() + (bytes + 7) / 8, 0);
+    memcpy(&*(key.end() - (bytes + 7) / 8), v, bytes);
+  };
+  whole(&fo, sizeof(fo));
+  whole(&r, sizeof(r));
+  for (int T : dsizes) key.push_back((uintptr_t)ctx->dag_lists[dag_list_key(ctx, T)].first.p);
+  return key;
+}
+
+// Factor the padded SPD matrix in A (destroyed) into Linv and logdiag (n_pad), and L into Lout if
+// given.  req is what this factorisation is asked for beyond that (FactorReq: the full GP's fit,
+// half the CUs, row signals, a pre-pass): no context member steers a call, the context holds the
+// options (ctx->fo), the buffers and the graph cache.  Returns 0 or a negative status; a non-PD
+// minor is reported through ctx->info (check_info).
 int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, double* logdiag,
-              int nreal, double* Lout) {
-  // the leaves and strip tasks write the lower triangles only: the strict-upper 128-tiles of
-  // Linv / Lout must already be zero for THIS layout (n_pad is the row stride)
+              int nreal, double* Lout, const FactorReq& req) {
+  // the leaves and strip tasks write the lower triangles only, the leaves' diagonal 16×16 tiles
+  // included: the strict-upper 128-tiles of Linv / Lout must already be zero for THIS layout (n_pad
+  // is the row stride) — every caller memsets the buffer when it allocates or resizes it
   if (!factor_zeroed(ctx, Linv, n_pad) || (Lout && !factor_zeroed(ctx, Lout, n_pad)))
     return fail(ctx, -1, "potrf_inv: factor buffer not zeroed for this size (internal contract)");
   // persistent blocks: task lists per size (uploaded once, before any capture) and one counter
@@ -554,7 +588,7 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
   // then a no-op or a dependency wait that timed out; the r3 suite runs 3c-3e.)
   std::vector<int> dsizes;
   int64_t dcnt = 0;
-  dag_blocks(ctx, n_pad / GPS_TILE, dsizes, dcnt);
+  dag_blocks(ctx, n_pad / GPS_TILE, req.full, dsizes, dcnt);
   for (int T : dsizes) {
     const int lk = dag_list_key(ctx, T);
     if (ctx->dag_lists.count(lk)) continue;
@@ -575,32 +609,19 @@ int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, d
   }
   auto eager = [&]() {
     ctx->sync_used = 0;
-    ctx->pre.join = nullptr;
     ctx->dag_cnt_used = 0;
     ctx->fplan = gps_ctx::FactorPlan{};
     return potrf_inv_rec(ctx, A, n_pad, Linv, n_pad, W, (int)(n_pad / GPS_TILE), logdiag,
-                         static_cast<int*>(ctx->info.p), 0, nreal, Lout, n_pad, true);
+                         static_cast<int*>(ctx->info.p), 0, nreal, Lout, n_pad, req, true, req.sig);
   };
   if (!ctx->graphs || ctx->prof || n_pad <= GPS_TILE) return eager();
   // capture: everything the recursion allocates must exist beforehand (no allocation inside a
   // capture), and the key names the buffers the sequence bakes in: the split-K workspaces first
   HIPCHK(ensure(ctx, ctx->ws_main, (size_t)kSplitWsDoubles * 8));
   HIPCHK(ensure(ctx, ctx->ws_side, (size_t)kSplitWsDoubles * 8));
-  const bool pre = ctx->pre.kind == PRE_FITC_Q;
-  std::vector<uintptr_t> key = {
-      (uintptr_t)A, (uintptr_t)n_pad, (uintptr_t)Linv, (uintptr_t)W, (uintptr_t)logdiag,
-      (uintptr_t)nreal, (uintptr_t)Lout, (uintptr_t)ctx->stream, (uintptr_t)ctx->side,
-      (uintptr_t)ctx->overlap, (uintptr_t)ctx->gemm_map, (uintptr_t)ctx->gemm_live, (uintptr_t)ctx->dag_full,
-      (uintptr_t)g_tiny_gemm, (uintptr_t)g_stream_k, (uintptr_t)g_slab_xcd, (uintptr_t)ctx->info.p, (uintptr_t)ctx->ws_main.p,
-      (uintptr_t)ctx->ws_side.p, (uintptr_t)pre,
-      // the pre-pass's operands (only when it is part of the sequence)
-      pre ? (uintptr_t)ctx->pre.n1 : 0, pre ? (uintptr_t)ctx->aux[0] : 0,
-      pre ? (uintptr_t)ctx->Knm.p : 0, pre ? (uintptr_t)ctx->fslab.p : 0,
-      pre ? (uintptr_t)ctx->fn_pad : 0, pre ? (uintptr_t)ctx->m_pad : 0, pre ? (uintptr_t)ctx->pre.sig : 0,
-      (uintptr_t)ctx->dag, (uintptr_t)ctx->dag_tiles,
-      (uintptr_t)(ctx->dag_full ? ctx->dag_tiles_full : 0), (uintptr_t)ctx->dag_kbatch, (uintptr_t)ctx->dag_tile_form, (uintptr_t)ctx->dag_group, (uintptr_t)ctx->dag_wgs, (uintptr_t)ctx->dag_half,
-      (uintptr_t)ctx->dag_cnt.p, (uintptr_t)ctx->sk_cnt.p, (uintptr_t)ctx->dag_sig};
-  for (int T : dsizes) key.push_back((uintptr_t)ctx->dag_lists[dag_list_key(ctx, T)].first.p);  // the task lists
+  const std::vector<uintptr_t> key = factor_key(
+      ctx, req, {(uintptr_t)A, (uintptr_t)n_pad, (uintptr_t)Linv, (uintptr_t)W, (uintptr_t)logdiag,
+                 (uintptr_t)nreal, (uintptr_t)Lout}, dsizes);
   for (auto& g : ctx->pgraphs)
     if (g.key == key) {
       g.last_use = ++ctx->graph_tick;
@@ -825,10 +846,10 @@ int gps_ctx_set_stream(gps_ctx* ctx, void* hip_stream) {
 int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
   if (int rc = bind(ctx)) return rc;
   switch (key) {
-    case GPS_OPT_OVERLAP: ctx->overlap = value != 0; return 0;
+    case GPS_OPT_OVERLAP: ctx->fo.overlap = value != 0; return 0;
     case GPS_OPT_GEMM_MAP:
       ARGCHK(value >= 0 && value <= 6, "GPS_OPT_GEMM_MAP must be in 0..6");
-      ctx->gemm_map = value;
+      ctx->fo.gemm_map = value;
       return 0;
     case GPS_OPT_AR_CHUNKS:
       ARGCHK(value >= 1 && value <= 64, "GPS_OPT_AR_CHUNKS must be in 1..64");
@@ -846,10 +867,10 @@ int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
       return 0;
     case GPS_OPT_GRAPH: ctx->graphs = value != 0; return 0;
     case GPS_OPT_PRED_PRE: ctx->pred_pre = value != 0; return 0;
-    case GPS_OPT_DAG: ctx->dag = value != 0; return 0;
+    case GPS_OPT_DAG: ctx->fo.dag = value != 0; return 0;
     case GPS_OPT_DAG_WGS:
       ARGCHK(value >= 0, "GPS_OPT_DAG_WGS must be >= 0");
-      ctx->dag_wgs = value;
+      ctx->fo.dag_wgs = value;
       return 0;
     case GPS_OPT_FITC_DEP: ctx->fitc_dep = value != 0; return 0;
     case GPS_OPT_DAG_ORDER:
@@ -858,26 +879,26 @@ int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
       return 0;
     case GPS_OPT_DAG_GROUP:
       ARGCHK(value >= 2 && value <= 4, "GPS_OPT_DAG_GROUP must be 2, 3 or 4");
-      ctx->dag_group = value;
+      ctx->fo.dag_group = value;
       return 0;
     case GPS_OPT_DAG_TILES:
       ARGCHK(value >= 2 && value <= 64, "GPS_OPT_DAG_TILES must be in 2..64");
-      ctx->dag_tiles = value;
+      ctx->fo.dag_tiles = value;
       return 0;
     case GPS_OPT_DAG_TILES_FULL:
       ARGCHK(value == 0 || (value >= 2 && value <= 64), "GPS_OPT_DAG_TILES_FULL must be 0 or in 2..64");
-      ctx->dag_tiles_full = value;
+      ctx->fo.dag_tiles_full = value;
       return 0;
     case GPS_OPT_DAG_KBATCH:
       ARGCHK(value >= 0 && (value & 15) <= 8 && (value >> 4 & 15) <= 3 && (value >> 9) == 0,
              "GPS_OPT_DAG_KBATCH must be B | g << 4 [| 256] with B in 0..8 and g in 0..3");
-      ctx->dag_kbatch = (value & 15) < 2 ? 0 : value;
+      ctx->fo.dag_kbatch = (value & 15) < 2 ? 0 : value;
       return 0;
-    case GPS_OPT_GEMM_LIVE: ctx->gemm_live = value != 0; return 0;
+    case GPS_OPT_GEMM_LIVE: ctx->fo.gemm_live = value != 0; return 0;
     case GPS_OPT_DAG_TILE_FORM:
       ARGCHK(value >= 0 && (value & 15) <= 8 && (value >> 8) == 0 && ((value & 15) || !value),
              "GPS_OPT_DAG_TILE_FORM must be 0 or minlen | d << 4 with minlen in 1..8 and d in 0..15");
-      ctx->dag_tile_form = value;
+      ctx->fo.dag_tile_form = value;
       return 0;
     default: return fail(ctx, -1, "unknown option");
   }
@@ -1091,7 +1112,8 @@ int factor_user(gps_ctx* ctx, int64_t n, const double* A, int64_t lda, bool want
   double* Lout = want_L ? ctx->t4.d() + np : nullptr;
   if (want_L) HIPCHK(zero_factor(ctx, Lout, np, ctx->stream));
   if (int rc = reset_info(ctx)) return rc;
-  if (int rc = potrf_inv(ctx, ctx->t1.d(), np, ctx->t2.d(), ctx->t3.d(), logdiag, (int)n, Lout))
+  if (int rc = potrf_inv(ctx, ctx->t1.d(), np, ctx->t2.d(), ctx->t3.d(), logdiag, (int)n, Lout,
+                         FactorReq{}))
     return rc;
   return check_info(ctx);
 }

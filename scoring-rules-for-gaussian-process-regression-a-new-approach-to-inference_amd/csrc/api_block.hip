@@ -247,7 +247,7 @@ int blockloo_folds(gps_ctx* ctx, const std::vector<int64_t>& bnd, int objective,
   // their schedules need ‖C_f‖∞: the bounds of all folds then come back in ONE host read instead
   // of a stream drain per fold.  C_f, r_f, w_f are kept per fold (the fold gradients
   // land in disjoint blocks: full GP).
-  const int es_streams = ctx->overlap ? (int)std::min<int64_t>(nfold, 4) : 1;
+  const int es_streams = ctx->fo.overlap ? (int)std::min<int64_t>(nfold, 4) : 1;
   const bool es_conc = esq && (es_streams > 1 || es_norm);
   if (es_norm) HIPCHK(ensure(ctx, ctx->escale, (size_t)(nfold + bp) * 8));
   std::vector<double> hscale(nfold, 0.0);
@@ -264,7 +264,8 @@ int blockloo_folds(gps_ctx* ctx, const std::vector<int64_t>& bnd, int objective,
   for (int f = 0; f < nfold; ++f) {
     const int64_t a = bnd[f], b = bnd[f + 1] - bnd[f];
     if ((rc = getP(f, a, b, ctx->bP.d(), bp))) return rc;
-    if ((rc = potrf_inv(ctx, ctx->bP.d(), bp, ctx->bL.d(), ctx->W.d(), ld, (int)b, nullptr)))
+    if ((rc = potrf_inv(ctx, ctx->bP.d(), bp, ctx->bL.d(), ctx->W.d(), ld, (int)b, nullptr,
+                        FactorReq{})))
       return rc;
     HIPCHK(launch_pad_copy(alpha + a, 1, af, 1, (int)b, 1, (int)bp, 1, 0, s));
     HIPCHK(launch_pad_copy(y + a, 1, yf, 1, (int)b, 1, (int)bp, 1, 0, s));
@@ -346,12 +347,8 @@ int blockloo_folds(gps_ctx* ctx, const std::vector<int64_t>& bnd, int objective,
                         want_grad ? g + a : nullptr, fs + 3 * f + 2)))
         return rc;
     }
-    for (int k = 1; k < nst; ++k) {
-      hipEvent_t join = sync_event(ctx);
-      if (!join) return fail(ctx, -2, "hipEventCreate failed");
-      HIPCHK(hipEventRecord(join, st[k]));
-      HIPCHK(hipStreamWaitEvent(s, join, 0));
-    }
+    for (int k = 1; k < nst; ++k)
+      if ((rc = fork_to(ctx, sync_event(ctx), st[k], s))) return rc;
     if (want_grad)
       for (int f = 0; f < nfold; ++f)
         if ((rc = gdone(f, bnd[f], bnd[f + 1] - bnd[f]))) return rc;
@@ -818,7 +815,7 @@ int gps_fitc_blockloo(gps_ctx* ctx, const double* theta, int n_ell, int nfold, i
   auto getW = [&](int fl, int64_t a, int64_t b, int64_t bpp, double* hl) -> int {
     HIPCHK(launch_fold_sum(ctx->bSg.d(), mm, nfl, fl, ctx->Kmm.d(), remote, 1.0, ctx->bBf.d(), mm, s));
     if (int rc2 = potrf_inv(ctx, ctx->bBf.d(), mp, ctx->bLf.d(), ctx->W.d(), ctx->bldf.d(), (int)m,
-                            nullptr))
+                            nullptr, FactorReq{}))
       return rc2;
     HIPCHK(launch_pad_copy(ctx->Knm.d() + a * mp, mp, ctx->bT.d(), mp, (int)b, (int)mp, (int)bpp,
                            (int)mp, 0, s));

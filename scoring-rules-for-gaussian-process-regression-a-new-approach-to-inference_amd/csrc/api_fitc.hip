@@ -167,8 +167,7 @@ int fitc_syrk_allreduce(gps_ctx* ctx, double* red, int64_t blen, int64_t tail) {
       Prof pr(ctx, "syrk_slab_sum", 0, 8.0 * (ks + 1) * (R1 - R0) * R1);
       HIPCHK(launch_sym_pack(ctx->slabB.d(), mp * mp, ks, r0, r1, (int)mp, red, s));
     }
-    HIPCHK(hipEventRecord(ctx->ar_ev[c], s));
-    HIPCHK(hipStreamWaitEvent(cs, ctx->ar_ev[c], 0));
+    if (int rc = fork_to(ctx, ctx->ar_ev[c], s, cs)) return rc;
     const int64_t e0 = (int64_t)r0 * (r0 + 1) / 2;
     const int64_t e1 = c + 1 == nch ? blen + tail : (int64_t)r1 * (r1 + 1) / 2;
     Prof pr(ctx, "allreduce_B", 0, 8.0 * (e1 - e0), cs);
@@ -195,11 +194,8 @@ int fitc_test_prepass(gps_ctx* ctx) {
   HIPCHK(ensure(ctx, ctx->Ksm, (size_t)ntp * mp * 8));
   HIPCHK(ensure(ctx, ctx->qm, ntp * 8));
   HIPCHK(ensure(ctx, ctx->fslab_pre, (size_t)tm * ntp * 8));
-  for (hipEvent_t* e : {&ctx->pre_fork, &ctx->pre_join})
-    if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(ctx->pre_fork, ctx->stream));
-  HIPCHK(hipStreamWaitEvent(a, ctx->pre_fork, 0));
   int rc;
+  if ((rc = fork_to(ctx, own_event(ctx->pre_fork), ctx->stream, a))) return rc;
   if ((rc = gram(ctx, "gram_ksm", ctx->fXt.d(), (int)nt, ctx->Z.d(), (int)m, ctx->fd, th, 0.0, 0, 0,
                  ctx->Ksm.d(), mp, (int)ntp, (int)mp, a)))
     return rc;
@@ -209,7 +205,7 @@ int fitc_test_prepass(gps_ctx* ctx) {
   p.out0 = ctx->fslab_pre.d(); p.ld_out = ntp;
   if ((rc = gemm(ctx, LAY_N, LAY_T, EPI_ROWSQ, p, a))) return rc;
   HIPCHK(launch_slab_sum(ctx->fslab_pre.d(), ntp, (int)tm, ntp, nullptr, ctx->qm.d(), a));
-  HIPCHK(hipEventRecord(ctx->pre_join, a));
+  HIPCHK(hipEventRecord(own_event(ctx->pre_join), a));
   ctx->f_pre = true;
   return 0;
 }
@@ -221,9 +217,7 @@ int fitc_test_prepass_b(gps_ctx* ctx) {
   const int64_t ntp = ctx->fnt_pad, mp = ctx->m_pad, tm = mp / GPS_TILE;
   hipStream_t a = ctx->aux[0];
   HIPCHK(ensure(ctx, ctx->qb, ntp * 8));
-  if (!ctx->preb_fork) HIPCHK(hipEventCreateWithFlags(&ctx->preb_fork, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(ctx->preb_fork, ctx->stream));
-  HIPCHK(hipStreamWaitEvent(a, ctx->preb_fork, 0));
+  if (int rc = fork_to(ctx, own_event(ctx->preb_fork), ctx->stream, a)) return rc;
   GemmParams p = gp0();
   p.A = ctx->Ksm.d(); p.lda = mp; p.B = ctx->Lb.d(); p.ldb = mp;
   p.M = (int)ntp; p.N = (int)mp; p.K = (int)mp; p.tri = TRI_K_LE_J;
@@ -301,22 +295,22 @@ int fitc_fit_core(gps_ctx* ctx, const double* theta, int n_ell, double obj[GPS_N
                  ctx->Am.d(), mp, (int)mp, (int)mp)))
     return rc;
   // (a persistent top level has no recursion step to overlap the pre-pass with)
-  const bool preq = ctx->pred_pre && mp > GPS_TILE && !dag_block(ctx, mp / GPS_TILE);
+  const bool preq = ctx->pred_pre && mp > GPS_TILE && !dag_block(ctx, mp / GPS_TILE, false);
   // this shard's rows of K(X, Z): with a pre-pass, first on the main stream (the q column tiles
   // [0, n1) then run on aux[0] inside Lm's captured factorisation, as soon as the top-level
   // Lm11⁻¹ is final); without one, on aux[0] beside Lm's factorisation, whose persistent blocks
   // leave half the CUs free (it needs only X, Z), joined before the q pass
-  const bool kside = !preq && ctx->overlap && !ctx->prof;
+  const bool kside = !preq && ctx->fo.overlap && !ctx->prof;
   // one persistent launch per m×m factorisation: the q and r row norms behind it (GPS_OPT_FITC_DEP)
-  const bool dep = kside && ctx->fitc_dep && dag_block(ctx, tm);
+  const bool dep = kside && ctx->fitc_dep && dag_block(ctx, tm, false);
   // a recursive m×m factorisation whose top-level L11 is one persistent launch: the q pre-pass
   // over L11⁻¹'s columns behind that launch (potrf_inv_rec, C5) when the pre-pass is at most 8192
   // tiles — about what the CUs beside the launch finish while it runs; a larger one would run
   // on at the dependent launch's column-by-column rate, below the paired order's.  Measured
   // (DESIGN §6.49): C5's rows per rank at N = 8 / 4 (3136 / 6256 tiles) 28.88 → 28.76 / 49.01 →
   // 48.81 ms, at N = 2 / 1 (12 512 / 25 008) 89.38 → 90.51 / 169.8 → 170.7
-  const bool pdep = preq && ctx->fitc_dep && ctx->overlap && !ctx->prof &&
-                    dag_block(ctx, tm / 2) && (np / GPS_TILE) * (tm / 2) <= 8192;
+  const bool pdep = preq && ctx->fitc_dep && ctx->fo.overlap && !ctx->prof &&
+                    dag_block(ctx, tm / 2, false) && (np / GPS_TILE) * (tm / 2) <= 8192;
   int* sig_m = nullptr;
   int* sig_b = nullptr;
   // ... and the r pre-pass behind Lb's top L11 block the same way when it is at most 4096 tiles
@@ -330,10 +324,8 @@ int fitc_fit_core(gps_ctx* ctx, const double* theta, int n_ell, double obj[GPS_N
     HIPCHK(hipMemsetAsync(ctx->dsig.p, 0, 2 * kSigInts * sizeof(int), s));
   }
   if (kside) {  // (dedicated events: the factorisation reuses its pool of sync events)
-    for (hipEvent_t* e : {&ctx->kn_fork, &ctx->kn_join})
-      if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->kn_fork, s));
-    HIPCHK(hipStreamWaitEvent(ctx->aux[0], ctx->kn_fork, 0));
+    if (!own_event(ctx->kn_join)) return fail(ctx, -2, "hipEventCreate failed");
+    if ((rc = fork_to(ctx, own_event(ctx->kn_fork), s, ctx->aux[0]))) return rc;
     if ((rc = gram(ctx, "gram_kmm", ctx->Z.d(), (int)m, ctx->Z.d(), (int)m, ctx->fd, th, 1e-3, 0,
                    1, ctx->Kmm.d(), mp, (int)mp, (int)mp, ctx->aux[0])))
       return rc;
@@ -350,17 +342,13 @@ int fitc_fit_core(gps_ctx* ctx, const double* theta, int n_ell, double obj[GPS_N
   }
   if (kside) HIPCHK(hipEventRecord(ctx->kn_join, ctx->aux[0]));
   const int64_t qn1 = preq ? (mp / GPS_TILE / 2) * GPS_TILE : 0;
-  ctx->pre.kind = preq ? PRE_FITC_Q : PRE_NONE;
-  ctx->pre.n1 = qn1;
-  ctx->pre.L = ctx->Lm.d();
-  ctx->pre.sig = pdep ? sig_m : nullptr;
-  ctx->dag_half = true;  // (the FITC m×m factorisations: see potrf_inv_rec's width)
-  ctx->dag_sig = dep ? sig_m : nullptr;
-  rc = potrf_inv(ctx, ctx->Am.d(), mp, ctx->Lm.d(), ctx->W.d(), ctx->ldm.d(), (int)m, nullptr);
-  ctx->dag_sig = nullptr;
-  ctx->pre.sig = nullptr;
-  ctx->dag_half = false;
-  ctx->pre.kind = PRE_NONE;
+  FactorReq req;  // (of both m×m factorisations: half the CUs, see dag_width; the q pre-pass)
+  req.half = 1;
+  req.pre.kind = preq ? PRE_FITC_Q : PRE_NONE;
+  req.pre.n1 = (int)qn1;
+  req.pre.sig = pdep ? sig_m : nullptr;
+  req.sig = dep ? sig_m : nullptr;
+  rc = potrf_inv(ctx, ctx->Am.d(), mp, ctx->Lm.d(), ctx->W.d(), ctx->ldm.d(), (int)m, nullptr, req);
   phase_mark(ctx, "kmm_lm");
   if (kside) HIPCHK(hipStreamWaitEvent(s, ctx->kn_join, 0));  // (before any return: Knm in flight)
   if (rc) return rc;
@@ -381,20 +369,15 @@ int fitc_fit_core(gps_ctx* ctx, const double* theta, int n_ell, double obj[GPS_N
   phase_mark(ctx, "q");
   // b_p = Kmnᵀ Λ⁻¹ y: one rank, an HBM-bound pass on aux[1] beside the SYRK (b is first read
   // by c = B⁻¹b after B's factorisation); sharded, it travels in the all-reduce with B
-  const bool bside = !shard && ctx->overlap && !ctx->prof;
-  if (bside) {
-    for (hipEvent_t* e : {&ctx->b_fork, &ctx->b_join})
-      if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->b_fork, s));
-    HIPCHK(hipStreamWaitEvent(ctx->aux[1], ctx->b_fork, 0));
-  }
+  const bool bside = !shard && ctx->fo.overlap && !ctx->prof;
+  if (bside && (rc = fork_to(ctx, own_event(ctx->b_fork), s, ctx->aux[1]))) return rc;
   {
     hipStream_t bs = bside ? ctx->aux[1] : s;
     Prof pr(ctx, "colred_b", 0, 8.0 * np * mp, bs);
     HIPCHK(launch_colred(ctx->Knm.d(), mp, (int)np, (int)mp, 0, ctx->ys.d(), nullptr, bvec,
                          nullptr, ctx->fslab.d(), bs));
   }
-  if (bside) HIPCHK(hipEventRecord(ctx->b_join, ctx->aux[1]));
+  if (bside) HIPCHK(hipEventRecord(own_event(ctx->b_join), ctx->aux[1]));
   // B_p = Kmnᵀ Λ⁻¹ Knm (lower tiles, split-K slabs); sharded: packed and all-reduced with b,
   // Σlogλ, Σy²/λ, in row blocks overlapped with the SYRK (ctx->ar_chunks); one
   // rank: the slab sum adds K̃mm and writes B = K̃mm + Σ slabs straight into Am (one launch)
@@ -407,23 +390,17 @@ int fitc_fit_core(gps_ctx* ctx, const double* theta, int n_ell, double obj[GPS_N
     phase_mark(ctx, "syrk");
   }
   if (bside) HIPCHK(hipStreamWaitEvent(s, ctx->b_join, 0));
-  if (pre_test && ctx->f_test && ctx->fnt > 0 && ctx->overlap && !ctx->prof)
+  if (pre_test && ctx->f_test && ctx->fnt > 0 && ctx->fo.overlap && !ctx->prof)
     if ((rc = fitc_test_prepass(ctx))) return rc;
   // --- B = K̃mm + Σ_p B_p, factor redundantly on every rank
   if (shard) HIPCHK(launch_sym_unpack(Bacc, (int)m, (int)mp, ctx->Kmm.d(), 0, ctx->Am.d(), s));
   // (the r pass's column tiles [0, qn1), like q's, as soon as the top-level Lb11⁻¹ is final)
-  ctx->pre.kind = preq ? PRE_FITC_Q : PRE_NONE;
-  ctx->pre.n1 = qn1;
-  ctx->pre.L = ctx->Lb.d();
-  ctx->pre.sig = pdep_b ? sig_b : nullptr;
-  // (the r pass behind Lb's factorisation as well — every column tile on aux[1], g = Knm c by a GEMV
+  req.pre.sig = pdep_b ? sig_b : nullptr;
+  req.sig = nullptr;  // (no top-level signals:
+  //  the r pass behind Lb's factorisation as well — every column tile on aux[1], g = Knm c by a GEMV
   //  after c — measured no faster: C4 11.84 vs 11.80 ms, profiles/r6b_fitc_dep_ab_c4.txt; the CUs
   //  Lb's factorisation leaves already run the test-side q* norms)
-  ctx->dag_half = true;
-  rc = potrf_inv(ctx, ctx->Am.d(), mp, ctx->Lb.d(), ctx->W.d(), ctx->ldb.d(), (int)m, nullptr);
-  ctx->dag_half = false;
-  ctx->pre.kind = PRE_NONE;
-  ctx->pre.sig = nullptr;
+  rc = potrf_inv(ctx, ctx->Am.d(), mp, ctx->Lb.d(), ctx->W.d(), ctx->ldb.d(), (int)m, nullptr, req);
   if (rc) return rc;
   phase_mark(ctx, "lb");
   HIPCHK(launch_dot(ctx->ldb.d(), nullptr, (int)mp, sm + 1, s));

@@ -70,9 +70,9 @@ int full_fit_core(gps_ctx* ctx, int kind, const double* theta, int n_ell) {
   if ((rc = gram(ctx, "gram_kff", ctx->X.d(), (int)n, ctx->X.d(), (int)n, ctx->d, ctx->th,
                  ctx->th.sn2, 1, 1, ctx->A.d(), np, (int)np, (int)np)))
     return rc;
-  ctx->dag_full = true;  // (the full GP's own block cap: see dag_block)
-  rc = potrf_inv(ctx, ctx->A.d(), np, ctx->Linv.d(), ctx->W.d(), ctx->logdiag.d(), (int)n, nullptr);
-  ctx->dag_full = false;
+  FactorReq req;
+  req.full = 1;  // (the full GP's own block cap, the live-extent hints: dag_block, potrf_inv_rec)
+  rc = potrf_inv(ctx, ctx->A.d(), np, ctx->Linv.d(), ctx->W.d(), ctx->logdiag.d(), (int)n, nullptr, req);
   if (rc) return rc;
   {
     Prof pr(ctx, "gemv_beta", 0, 4.0 * (double)np * np);

@@ -20,6 +20,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gps_internal.h"
@@ -108,8 +109,40 @@ extern std::map<long long, std::weak_ptr<LocalGroup>> g_groups;
 }  // namespace gpsapi
 using namespace gpsapi;
 
-
 enum { PRE_NONE = 0, PRE_FITC_Q = 1 };
+
+// What one factorisation is asked for: potrf_inv's argument, nothing of it lives in the context.
+// The default is what the folds, the joint blocks and gps_potrf pass.  Like FactorOpts it enters
+// the graph-cache key whole (factor_key), hence ints and pointers without padding.
+struct FactorReq {
+  int full = 0;                        // the full GP's fit: GPS_OPT_DAG_TILES_FULL is its block cap,
+                                       // and its matrix is diag(A, I) (the live-extent hints)
+  int half = 0;                        // leave half the CUs to a side stream (FITC's m×m ones)
+  int* sig = nullptr;                  // row signals (kSig*, zeroed by the caller) of the top-level
+                                       // block, which then must be one persistent launch
+  struct Pre {                         // work launched once the top-level L11⁻¹ is final:
+    int kind = PRE_NONE, n1 = 0;       // PRE_FITC_Q (the q column tiles [0, n1), on aux[0])
+    int* sig = nullptr;                // row signals: the pre-pass runs behind the L11 block
+  } pre;                               // (GPS_OPT_FITC_DEP, on aux[1]; zeroed by the caller)
+};
+// The options a captured factorisation sequence reads: a member added here is in the key.  (Not
+// read by it: graphs, pred_pre, fitc_dep, ar_chunks, the Gram option; dag_order: see factor_key.)
+struct FactorOpts {
+  int overlap = 1;                     // GPS_OPT_OVERLAP
+  int gemm_map = 0;                    // GPS_OPT_GEMM_MAP: tile-order override (A/B measurements)
+  int gemm_live = 1;                   // GPS_OPT_GEMM_LIVE: the GEMMs' live-extent hints (gemm())
+  int dag = 1;                         // GPS_OPT_DAG: persistent factorisation of the bottom blocks
+  int dag_tiles = 20;                  // GPS_OPT_DAG_TILES
+  int dag_tiles_full = 40;             // GPS_OPT_DAG_TILES_FULL: the full GP's cap (0: dag_tiles)
+  int dag_kbatch = 8 | 256;            // GPS_OPT_DAG_KBATCH: B | g << 4 | 256 (B < 2: every term a
+                                       // task; 256: in blocks above dag_tiles only)
+  int dag_tile_form = 2 | 2 << 4;      // GPS_OPT_DAG_TILE_FORM: minlen | d << 4 (0: strips only)
+  int dag_group = 3;                   // GPS_OPT_DAG_GROUP
+  int dag_wgs = 0;                     // GPS_OPT_DAG_WGS (0: automatic, see dag_width)
+  int tiny_gemm = 0, stream_k = 0, slab_xcd = 0;  // the process-wide g_* as read at key time
+};
+static_assert(std::has_unique_object_representations_v<FactorReq> &&
+              std::has_unique_object_representations_v<FactorOpts>, "compared as words: no padding");
 
 struct gps_ctx {
   int device = 0;
@@ -117,31 +150,16 @@ struct gps_ctx {
   bool own_stream = true;
   hipStream_t side = nullptr;          // second stream for off-critical-path GEMMs
   hipStream_t aux[2] = {nullptr, nullptr};  // two more streams (concurrent energy-score folds)
-  bool overlap = true;                 // GPS_OPT_OVERLAP
-  int gemm_map = 0;                    // GPS_OPT_GEMM_MAP: tile-order override (A/B measurements)
+  FactorOpts fo;                       // the options a factorisation's captured sequence reads
   int ar_chunks = 4;                   // GPS_OPT_AR_CHUNKS: row blocks of the FITC B all-reduce
   std::vector<hipEvent_t> ar_ev;       // their hand-offs to the comm stream (aux[1])
-                                       // goes to the side stream (a fork/join costs ~13 us, but
-                                       // forking every level measured best: 128.3 vs 129.1 ms)
   int ncu = 0;
   std::vector<hipEvent_t> sync_ev;     // fork/join events (timing disabled)
   size_t sync_used = 0;
   bool graphs = true;                  // GPS_OPT_GRAPH: replay the factorisation from a hipGraph
   bool pred_pre = true;                // GPS_OPT_PRED_PRE
-  bool dag = true;                     // GPS_OPT_DAG: persistent factorisation of the bottom blocks
-  int dag_tiles = 20;                  // GPS_OPT_DAG_TILES
-  int dag_group = 3;                   // GPS_OPT_DAG_GROUP
-  int dag_wgs = 0;                     // GPS_OPT_DAG_WGS (0: automatic, see dag_width)
   int dag_order = 1;                   // GPS_OPT_DAG_ORDER
-  int dag_tiles_full = 40;             // GPS_OPT_DAG_TILES_FULL: the full GP's cap (0: dag_tiles)
-  int dag_kbatch = 8 | 256;            // GPS_OPT_DAG_KBATCH: B | g << 4 | 256 (B < 2: every term a
-                                       // task; 256: in blocks above dag_tiles only)
-  int dag_tile_form = 2 | 2 << 4;      // GPS_OPT_DAG_TILE_FORM: minlen | d << 4 (0: strips only)
-  bool dag_full = false;               // this factorisation is full_fit_core's (dag_tiles_full applies)
-  bool gemm_live = true;               // GPS_OPT_GEMM_LIVE: the GEMMs' live-extent hints (gemm())
-  bool dag_half = false;               // this factorisation leaves half the CUs to a side stream
   bool fitc_dep = true;                // GPS_OPT_FITC_DEP: the q row norms behind Lm's factorisation
-  int* dag_sig = nullptr;              // the top-level persistent launch's row signals (kSig*), if any
   DBuf dsig;                           // the FITC signal block of Lm's factorisation (kSigInts ints)
   std::map<int, std::pair<DBuf, int>> dag_lists;  // per dag_list_key (T, order, K batches, tile form): device task list, length
   // factor buffers (L⁻¹, L) known to hold zeros for a padded size: potrf_inv writes their lower
@@ -151,14 +169,6 @@ struct gps_ctx {
   DBuf dag_cnt;                        // arrival counters of every persistent launch of a call
   DBuf sk_cnt;                         // stream-K tail tickets of the main stream's GEMMs (zero)
   int64_t dag_cnt_used = 0;
-  struct PrePass {                     // work potrf_inv launches on aux[0] once the top-level
-    int kind = 0;                      // L11⁻¹ is final: PRE_FITC_Q (the q column tiles [0, n1))
-    int64_t n1 = 0;
-    const double* L = nullptr;         // the top-level L⁻¹
-    hipEvent_t join = nullptr;         // waited by the top-level call before it returns
-    int* sig = nullptr;                // row signals: the pre-pass runs behind the L11 block
-                                       // (GPS_OPT_FITC_DEP; zeroed by the caller)
-  } pre;
   struct FactorPlan {                  // what the last potrf_inv ran (gps_potrf_diag): stand-alone
     int leaves = 0, dags = 0;          // leaf launches, persistent launches with their smallest
     int dag_tmin = 0, dag_tmax = 0;    // and largest T, the recursion's GEMM launches, and whether
@@ -170,8 +180,8 @@ struct gps_ctx {
     uint64_t last_use = 0;
     FactorPlan plan;                   // the launches it holds
   };
-  std::vector<PotrfGraph> pgraphs;     // keyed by buffers, sizes, streams, options; least recently
-                                       // used evicted past kMaxGraphs; dropped with their buffers
+  std::vector<PotrfGraph> pgraphs;     // keyed by factor_key; least recently used evicted past
+                                       // kMaxGraphs; dropped with the buffers their keys name
   uint64_t graph_tick = 0;
   int64_t graph_overflow = 0;          // (kept for the stats layout: always 0 since round 4)
   int64_t graph_dropped = 0;           // execs destroyed because a buffer they bake in was freed
@@ -317,10 +327,11 @@ hipError_t drop_graphs_in(gps_ctx* ctx, const void* p, size_t bytes);
 void forget_zeroed(gps_ctx* ctx, const void* p, size_t bytes);
 hipError_t ensure(gps_ctx* ctx, DBuf& b, size_t bytes);
 void release(gps_ctx* ctx, DBuf& b);
-int get_event(gps_ctx* c);
 int phase_event(gps_ctx* c, hipStream_t st);
 void phase_mark(gps_ctx* c, const char* name);
 hipEvent_t sync_event(gps_ctx* c);
+hipEvent_t own_event(hipEvent_t& e);
+int fork_to(gps_ctx* ctx, hipEvent_t e, hipStream_t from, hipStream_t to);
 GemmParams gp0();
 const char* gemm_tag(int al, int bl, int epi, const GemmParams& p);
 double gemm_flops(const GemmParams& p);
@@ -333,22 +344,14 @@ int pred_rows(gps_ctx* ctx, int64_t r0, int64_t r1, const double* w, hipStream_t
 int fitc_rowsq_cols(gps_ctx* ctx, const double* Lx, int64_t c0, int64_t c1, hipStream_t st);
 int fitc_rowsq_dep(gps_ctx* ctx, const double* L, int* sig, int64_t ncols, int mode,
                    hipStream_t st, int64_t nb_dag);
-int dag_list_key(const gps_ctx* ctx, int64_t nb);
-int dag_tf(const gps_ctx* ctx, int64_t nb);
-int dag_kb(const gps_ctx* ctx, int64_t nb);
-int dag_kg(const gps_ctx* ctx, int64_t nb);
-bool dag_block(const gps_ctx* ctx, int64_t nb);
-void dag_blocks(const gps_ctx* ctx, int64_t nb, std::vector<int>& sizes, int64_t& cnt);
+bool dag_block(const gps_ctx* ctx, int64_t nb, bool full);
 int dag_width(const gps_ctx* ctx, int64_t nb, bool half);
-int potrf_inv_rec(gps_ctx* ctx, double* A, int64_t lda, double* Linv, int64_t ldl, double* W,
-                  int nb, double* logdiag, int* info, int base, int nreal, double* Lout,
-                  int64_t ldlo, bool top = false);
 size_t potrf_ws_doubles(int64_t n_pad);
 int reset_info(gps_ctx* ctx);
 hipError_t zero_factor(gps_ctx* ctx, double* p, int64_t n_pad, hipStream_t s);
 bool factor_zeroed(const gps_ctx* ctx, const double* p, int64_t n_pad);
 int potrf_inv(gps_ctx* ctx, double* A, int64_t n_pad, double* Linv, double* W, double* logdiag,
-              int nreal, double* Lout);
+              int nreal, double* Lout, const FactorReq& req);
 int check_info(gps_ctx* ctx);
 int set_theta(gps_ctx* ctx, Theta& th, int kind, const double* theta, int n_ell, int d);
 int upload(gps_ctx* ctx, DBuf& b, const double* h, int64_t rows, int64_t cols, int64_t rows_pad);

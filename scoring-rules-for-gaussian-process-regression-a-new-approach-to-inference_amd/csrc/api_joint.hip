@@ -198,7 +198,8 @@ static int predict_joint(gps_ctx* ctx, int model, int nblock, int objective, int
     const JointVec jv = joint_vec(ctx, bp);
     HIPCHK(launch_joint_resid(yt + a, jv.mu, (int)b, (int)bp, jv.r, s));
     if (!es) {  // ½b·log2π + ½log|Sigma| + ½‖L⁻¹r‖²
-      if ((rc = potrf_inv(ctx, ctx->jS.d(), bp, ctx->jL.d(), ctx->jW.d(), jv.ld, (int)b, nullptr)))
+      if ((rc = potrf_inv(ctx, ctx->jS.d(), bp, ctx->jL.d(), ctx->jW.d(), jv.ld, (int)b, nullptr,
+                          FactorReq{})))
         return rc;
       HIPCHK(launch_gemv_lower(ctx->jL.d(), bp, jv.r, jv.t, (int)bp, s));
       HIPCHK(launch_joint_dss(jv.ld, jv.t, (int)b, jv.vals + f, s));
@@ -255,7 +256,7 @@ static int predict_draws(gps_ctx* ctx, int model, int64_t r0, int64_t r1, int ns
   const JointVec jv = joint_vec(ctx, bp);
   if ((rc = reset_info(ctx))) return rc;
   if ((rc = potrf_inv(ctx, ctx->jS.d(), bp, ctx->jL.d(), ctx->jW.d(), jv.ld, (int)b,
-                      ctx->jLo.d())))
+                      ctx->jLo.d(), FactorReq{})))
     return rc;
   if ((rc = check_info(ctx))) return rc;
   HIPCHK(hipMemsetAsync(ctx->jxi.p, 0, (size_t)sp * bp * 8, s));
