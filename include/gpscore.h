@@ -64,7 +64,9 @@ enum {
  * and gps_full_grad_tall / gps_full_train_tall, their block-LOO siblings
  * gps_full_blockloo_grad_tall / gps_full_blockloo_train_tall and
  * gps_fitc_blockloo_grad_tall / gps_fitc_blockloo_train_tall, and the vector-layer
- * diagnostic gps_vec_diag.
+ * diagnostic gps_vec_diag, and the validated fits gps_full_train_tall_va /
+ * gps_full_blockloo_train_tall_va and gps_fitc_train_tall_va /
+ * gps_fitc_blockloo_train_tall_va.
  * The binding refuses a mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -817,6 +819,45 @@ int gps_fitc_blockloo_train_tall(gps_ctx* ctx, int objective, int nfold, int64_t
                                  const double* yt, int64_t nt, int flags, double* theta_out,
                                  double* z_out, double* values, double* thetas, double* obj,
                                  double* mu, double* var, double* sc, int* info, int* steps_done);
+
+/* ---- the tall FITC fits with a validation set scored step by step -----------------
+ * gps_fitc_train_tall and gps_fitc_blockloo_train_tall with every problem's own validation rows Xv
+ * (nprob·nv·d) and targets yv (nprob·nv) scored INSIDE the fit: K20's commented-out validation
+ * series (K20:258-264, 469-476, 737-743), from Lm⁻¹, Lb⁻¹ and c as the step's forward left them.
+ * The argument lists are the plain calls' with Xv, yv, nv, va_every in front of Xt and va_sc, va_z
+ * in front of info; everything else means what it means there, and the fit itself — theta_out,
+ * z_out, values, thetas, obj, mu, var, sc, info, steps_done — is bitwise what those calls return.
+ * Checkpoints, the final row (nva − 1, nva = ceil(itr / va_every) + 1, honouring
+ * GPS_BATCH_STALE_NOISE), the failure rule (a failed problem keeps the rows it reached, NaN in
+ * every later row, the final row included; on the block path a fit that fails in its fold work
+ * after a good forward keeps that step's row) and the refusals (1 <= nv <= 2^24, 1 <= va_every <=
+ * 2^20, Xv, yv and va_sc required) are those of gps_full_train_tall_va above; a row's parameters
+ * are θ AND Z before step i with that step's own σ².  va_sc holds nprob·nva·GPS_N_SC doubles.
+ * va_z (nprob·nva·m·d, may be NULL: no Z is kept) receives the Z of every row — the SGD steps move
+ * Z, and the series of θ alone does not name a row's model; its last row is z_out.  Each row of
+ * va_sc is bitwise the sc of an itr = 0 call of the plain entry point at that row's θ and Z with
+ * Xt = Xv, yt = yv, and is independent of nprob, position and launch split.  The 8 GiB guard counts
+ * Xv, yv, va_sc and va_z.  LDS and workspace are the plain calls'; a launch runs at most the plain
+ * rule's steps and at most max(1, floor(4096 / nv)·va_every): its checkpoints stream at most 4096
+ * validation rows (or one checkpoint's), about nv·m² FMAs a checkpoint. */
+int gps_fitc_train_tall_va(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                           const double* y, int64_t n, int d, const double* Z0, int m,
+                           const double* theta0, int n_ell, int64_t itr, double lr, double lr_z,
+                           const double* Xv, const double* yv, int64_t nv, int64_t va_every,
+                           const double* Xt, const double* yt, int64_t nt, int flags,
+                           double* theta_out, double* z_out, double* values, double* thetas,
+                           double* obj, double* mu, double* var, double* sc, double* va_sc,
+                           double* va_z, int* info, int* steps_done);
+int gps_fitc_blockloo_train_tall_va(gps_ctx* ctx, int objective, int nfold, int64_t nprob,
+                                    const double* X, const double* y, int64_t n, int d,
+                                    const double* Z0, int m, const double* theta0, int n_ell,
+                                    int64_t itr, double lr, double lr_z, const double* Xv,
+                                    const double* yv, int64_t nv, int64_t va_every,
+                                    const double* Xt, const double* yt, int64_t nt, int flags,
+                                    double* theta_out, double* z_out, double* values,
+                                    double* thetas, double* obj, double* mu, double* var,
+                                    double* sc, double* va_sc, double* va_z, int* info,
+                                    int* steps_done);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------- */
 int gps_comm_unique_id(char uid[128]);

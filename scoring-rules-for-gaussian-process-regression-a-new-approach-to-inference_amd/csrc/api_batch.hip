@@ -8,6 +8,8 @@
 //                                                                    kernels_batch_full_tall_block.hip
 //   gps_fitc_blockloo_{grad,train}_tall  the tall FITC GPs on the block-LOO DSS / KC objectives
 //                                                                    kernels_batch_fitc_tall_block.hip
+//   gps_fitc_train_tall_va, gps_fitc_blockloo_train_tall_va  the two tall FITC fits with a
+//                                  validation set scored inside the fit, same files
 //   gps_full_es_{grad,train}_tall  the tall full GPs on the block-LOO energy score, the fold work
 //                                  on one workgroup per (problem, fold)
 //                                                                    kernels_batch_full_tall_es.hip
@@ -20,7 +22,7 @@
 //            (its workspace is read in 16-byte pieces)
 //   btint    info | steps_done
 //   btout    GRAD: obj | grad | grad_z | value | fold_values (the last two: block-LOO);
-//            TRAIN: values | thetas | obj | mu | var | sc | va_sc
+//            TRAIN: values | thetas | obj | mu | var | sc | va_sc | va_z (FITC VA, when asked for)
 // Every call uploads all it reads, so nothing is carried from one batch call to the next; the
 // resident full-GP / FITC data, any fit and the test buffers are not touched, and nothing is
 // sharded, so a communicator does not matter.  A path is one Path constant: its limit on n, its
@@ -47,6 +49,7 @@ struct Block {
   int64_t draw_sets = 0;
   int num_sim = 0;
   double beta = 0.0;
+  BatchVaParams va = {};  // the FITC VA paths' validation rows and outputs (device)
 };
 
 template <class P>
@@ -63,6 +66,8 @@ struct Path {
                        hipStream_t s);
   bool block;                       // the objective is a GPS_BLOCK_* code over nfold folds
   bool es = false;                  // that code is GPS_BLOCK_ES: draws, num_sim and β come with it
+  // a VA path whose steps-per-launch rule also caps the validation rows a launch streams
+  int (*va_steps)(int64_t n, int64_t nv, int64_t va_every) = nullptr;
 };
 
 const Path<BatchParams> kFull = {
@@ -139,6 +144,29 @@ const Path<BatchFitcParams> kFitcTallBlock = {
           BatchFitcTallBlockParams{p, ws, stride, b.nfold, b.value, b.fold_values}, s);
     },
     true};
+// the two tall FITC paths with a validation set scored inside the fit: training calls
+// only, the grad tags are never used; the validation members travel in Block
+const Path<BatchFitcParams> kFitcTallVa = {
+    GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_va_grad",
+    "batch_fitc_tall_va_train",
+    [](int64_t n, int m, int, int) { return batch_fitc_tall_ws_doubles(n, m); }, false,
+    batch_fitc_tall_steps,
+    [](gps_ctx*, const BatchFitcParams& p, double* ws, int64_t stride, const Block& b,
+       hipStream_t s) {
+      return launch_batch_fitc_tall_va(BatchFitcTallVaParams{{p, ws, stride}, b.va}, s);
+    },
+    false, false, batch_fitc_tall_va_steps};
+const Path<BatchFitcParams> kFitcTallBlockVa = {
+    GPS_BATCH_FITC_TALL_MAX_N, "batch: n must be in 1..2048", "batch_fitc_tall_block_va_grad",
+    "batch_fitc_tall_block_va_train",
+    [](int64_t n, int m, int nfold, int) { return batch_fitc_tall_block_ws_doubles(n, m, nfold); },
+    false, batch_fitc_tall_block_steps,
+    [](gps_ctx*, const BatchFitcParams& p, double* ws, int64_t stride, const Block& b,
+       hipStream_t s) {
+      return launch_batch_fitc_tall_block_va(
+          BatchFitcTallBlockVaParams{{p, ws, stride, b.nfold, b.value, b.fold_values}, b.va}, s);
+    },
+    true, false, batch_fitc_tall_block_va_steps};
 const Path<BatchParams> kFullTallEs = {
     GPS_BATCH_FULL_TALL_MAX_N, "batch: n must be in 1..512", "batch_full_tall_es_grad",
     "batch_full_tall_es_train",
@@ -223,6 +251,7 @@ struct Va {
   const double *Xv, *yv;
   int64_t nv, va_every;
   double* va_sc;
+  double* va_z = nullptr;  // the FITC calls' Z of every row, or NULL
 };
 
 // Sizes the four buffers (nt test rows and nv validation rows a problem, n_out output doubles, n_ws
@@ -372,7 +401,7 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   const int64_t n_in =
       nprob * a.n * (a.d + 1) + nprob * (nt + nv) * (a.d + 1) + nprob * nz + a.n_draws();
   const int64_t n_out = nprob * itr * (1 + nth) + nprob * (GPS_N_OBJ + 2 * nt + GPS_N_SC) +
-                        nprob * nva * GPS_N_SC;
+                        nprob * nva * GPS_N_SC + (va && va->va_z ? nprob * nva * nz : 0);
   const int64_t stride = path.ws ? path.ws(a.n, a.m, a.nfold, a.num_sim) : 0;
   const int64_t n_ws = nprob * stride;
   ARGCHK(n_in <= kMaxDoubles && n_out <= kMaxDoubles && n_ws <= kMaxDoubles, kTooBig);
@@ -394,29 +423,37 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   p.mu = p.obj + nprob * GPS_N_OBJ;
   p.var = p.mu + nprob * nt;
   p.sc = p.var + nprob * nt;
-  if constexpr (!kFitc<P>)
-    if (va) {  // Xv | yv behind the test rows and the draws, va_sc behind sc
-      p.xv = xt_dev + nprob * nt * (a.d + 1) + a.n_draws();
-      p.yv = p.xv + nprob * nv * a.d;
-      p.nv = (int)nv;
-      p.va_every = (int)va->va_every;
-      p.va_sc = p.sc + nprob * GPS_N_SC;
+  BatchVaParams dv = {};
+  if (va) {  // Xv | yv behind the test rows and the draws, va_sc | va_z behind sc
+    dv.xv = xt_dev + nprob * nt * (a.d + 1) + a.n_draws();
+    dv.yv = dv.xv + nprob * nv * a.d;
+    dv.nv = (int)nv;
+    dv.va_every = (int)va->va_every;
+    dv.va_sc = p.sc + nprob * GPS_N_SC;
+    dv.va_z = va->va_z ? dv.va_sc + nprob * nva * GPS_N_SC : nullptr;
+    if constexpr (!kFitc<P>) {
+      p.xv = dv.xv;
+      p.yv = dv.yv;
+      p.nv = dv.nv;
+      p.va_every = dv.va_every;
+      p.va_sc = dv.va_sc;
     }
+  }
   std::vector<double> stale((size_t)nprob);  // before any step: θ0's own noise
   for (int64_t q = 0; q < nprob; ++q) stale[(size_t)q] = a.theta[q * nth + nth - 1];
   if (int rc = upload(ctx, a, p, Xt, yt, stale.data())) return rc;
-  if constexpr (!kFitc<P>)
-    if (va) {
-      HIPCHK(hipMemcpyAsync((void*)p.xv, va->Xv, (size_t)(nprob * nv * a.d) * 8,
-                            hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipMemcpyAsync((void*)p.yv, va->yv, (size_t)(nprob * nv) * 8,
-                            hipMemcpyHostToDevice, ctx->stream));
-    }
+  if (va) {
+    HIPCHK(hipMemcpyAsync((void*)dv.xv, va->Xv, (size_t)(nprob * nv * a.d) * 8,
+                          hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync((void*)dv.yv, va->yv, (size_t)(nprob * nv) * 8, hipMemcpyHostToDevice,
+                          ctx->stream));
+  }
   {
     // no launch runs more than path.steps(n) steps; θ, Z, the stale σ², info and steps_done stay
     // in device memory between the launches, the last one adds the final pass
     Prof pr(ctx, path.train_tag, 0, 0);
-    const int64_t per = path.steps(a.n);
+    const int64_t per =
+        va && path.va_steps ? path.va_steps(a.n, nv, va->va_every) : path.steps(a.n);
     int64_t step = 0;
     do {
       const int64_t ns = std::min<int64_t>(itr - step, per);
@@ -425,7 +462,7 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
       p.do_final = step + ns == itr;
       HIPCHK(path.launch(ctx, p, ws, stride,
                          Block{a.nfold, nullptr, nullptr, p.y + nprob * a.n + nprob * nt * (a.d + 1),
-                               a.draw_sets, a.num_sim, a.beta},
+                               a.draw_sets, a.num_sim, a.beta, dv},
                          ctx->stream));
       step += ns;
     } while (step < itr);
@@ -439,9 +476,10 @@ int train_call(gps_ctx* ctx, const Path<P>& path, const Problem& a, int64_t itr,
   if (int rc = download(ctx, mu, p.mu, nprob * nt)) return rc;
   if (int rc = download(ctx, var, p.var, nprob * nt)) return rc;
   if (int rc = download(ctx, scored ? sc : nullptr, p.sc, nprob * GPS_N_SC)) return rc;
-  if constexpr (!kFitc<P>)
-    if (va)
-      if (int rc = download(ctx, va->va_sc, p.va_sc, nprob * nva * GPS_N_SC)) return rc;
+  if (va) {
+    if (int rc = download(ctx, va->va_sc, dv.va_sc, nprob * nva * GPS_N_SC)) return rc;
+    if (int rc = download(ctx, va->va_z, dv.va_z, nprob * nva * nz)) return rc;
+  }
   if (int rc = download(ctx, info, p.info, nprob)) return rc;
   if (int rc = download(ctx, steps_done, p.steps_done, nprob)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -621,6 +659,37 @@ int gps_fitc_blockloo_train_tall(gps_ctx* ctx, int objective, int nfold, int64_t
                     {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell, nfold}, itr, lr, lr_z,
                     Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc, info,
                     steps_done);
+}
+
+int gps_fitc_train_tall_va(gps_ctx* ctx, int objective, int64_t nprob, const double* X,
+                           const double* y, int64_t n, int d, const double* Z0, int m,
+                           const double* theta0, int n_ell, int64_t itr, double lr, double lr_z,
+                           const double* Xv, const double* yv, int64_t nv, int64_t va_every,
+                           const double* Xt, const double* yt, int64_t nt, int flags,
+                           double* theta_out, double* z_out, double* values, double* thetas,
+                           double* obj, double* mu, double* var, double* sc, double* va_sc,
+                           double* va_z, int* info, int* steps_done) {
+  const Va va = {Xv, yv, nv, va_every, va_sc, va_z};
+  return train_call(ctx, kFitcTallVa, {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell}, itr,
+                    lr, lr_z, Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc,
+                    info, steps_done, &va);
+}
+
+int gps_fitc_blockloo_train_tall_va(gps_ctx* ctx, int objective, int nfold, int64_t nprob,
+                                    const double* X, const double* y, int64_t n, int d,
+                                    const double* Z0, int m, const double* theta0, int n_ell,
+                                    int64_t itr, double lr, double lr_z, const double* Xv,
+                                    const double* yv, int64_t nv, int64_t va_every,
+                                    const double* Xt, const double* yt, int64_t nt, int flags,
+                                    double* theta_out, double* z_out, double* values,
+                                    double* thetas, double* obj, double* mu, double* var,
+                                    double* sc, double* va_sc, double* va_z, int* info,
+                                    int* steps_done) {
+  const Va va = {Xv, yv, nv, va_every, va_sc, va_z};
+  return train_call(ctx, kFitcTallBlockVa,
+                    {0, objective, nprob, X, y, n, d, Z0, m, theta0, n_ell, nfold}, itr, lr, lr_z,
+                    Xt, yt, nt, flags, theta_out, z_out, values, thetas, obj, mu, var, sc, info,
+                    steps_done, &va);
 }
 
 }  // extern "C"

@@ -379,6 +379,41 @@ constexpr int kBatchFitcTallBlockDiv = 2;
 int batch_fitc_tall_block_steps(int64_t n);
 hipError_t launch_batch_fitc_tall_block(const BatchFitcTallBlockParams& p, hipStream_t s);
 
+// the two tall FITC paths with a validation set scored inside the fit (batch_fitc_tall_va_kernel,
+// batch_fitc_tall_block_va_kernel).  The validation members live in structs of the new
+// kernels' own that hold the old struct FIRST, so no argument of an old kernel moves (§34 found
+// that new members inside a shared struct changed the register allocation of kernels that never
+// read them).  Step i = step0 + st of a launch is a checkpoint when i % va_every == 0: directly
+// after its forward() the kernel scores the nv validation rows at that forward's θ, Z and σ² into
+// row i / va_every of va_sc and copies the current Z into va_z; the final pass adds row nva − 1,
+// nva = ceil(itr / va_every) + 1.  A failed problem keeps the rows it reached and gets NaN in the
+// rest.  LDS and workspace are the plain kernels'.
+struct BatchVaParams {
+  const double* xv; const double* yv;   // [nprob][nv][d], [nprob][nv]
+  int nv, va_every;
+  double* va_sc;                        // [nprob][nva][GPS_N_SC]
+  double* va_z;                         // [nprob][nva][m][d], or NULL: no Z is kept
+};
+struct BatchFitcTallVaParams {
+  BatchFitcTallParams t;
+  BatchVaParams va;
+};
+struct BatchFitcTallBlockVaParams {
+  BatchFitcTallBlockParams t;
+  BatchVaParams va;
+};
+// SGD steps one VA launch may run: never more than the plain rule's, and at most
+// kBatchFitcVaRowBudget validation rows streamed by its checkpoints, so that they add at most ~5 ms
+// to a launch (a row measured 1.07 µs at m = 32, d = 16: 4.4 ms for the budget); always
+// at least one step.  A window of k steps holds at most ceil(k / va_every) checkpoints, so k = max(1,
+// floor(budget / nv)·va_every): a function of n, nv and va_every alone.
+constexpr int64_t kBatchFitcVaRowBudget = 4096;
+int batch_fitc_tall_va_steps(int64_t n, int64_t nv, int64_t va_every);
+int batch_fitc_tall_block_va_steps(int64_t n, int64_t nv, int64_t va_every);
+// BATCH_MODE_TRAIN only: refuse BATCH_MODE_GRAD, a NULL xv, yv or va_sc, nv < 1 and va_every < 1
+hipError_t launch_batch_fitc_tall_va(const BatchFitcTallVaParams& p, hipStream_t s);
+hipError_t launch_batch_fitc_tall_block_va(const BatchFitcTallBlockVaParams& p, hipStream_t s);
+
 // batches of full GPs of up to 512 rows, one workgroup per problem (kernels_batch_full_tall.hip,
 // DESIGN §24): BatchParams' model and semantics with the n×n arrays in a per-problem device
 // workspace instead of LDS and the O(n³) work on the FP64 matrix instruction, tile by tile.  Why

@@ -31,6 +31,7 @@
 // The chunk helpers are batch_fitc_tall_shared.h's; the step driver in the __global__ function is
 // kernels_batch_fitc_tall.hip's text, copied (§27 says what was shared and what was not).
 #include "batch_fitc_tall_shared.h"
+#include "batch_fitc_tall_va.h"
 
 namespace gps {
 
@@ -803,6 +804,99 @@ __global__ __launch_bounds__(FT) void batch_fitc_tall_block_kernel(BatchFitcTall
   }
 }
 
+// batch_fitc_tall_block_kernel plus the validation rows, as batch_fitc_tall_va_kernel:
+// the checkpoint stands between forward() and block_gradient(), so a fit that fails in its fold
+// work after a good forward keeps that step's row (§34's rule).
+__global__ __launch_bounds__(FT) void batch_fitc_tall_block_va_kernel(
+    BatchFitcTallBlockVaParams vp) {
+  extern __shared__ double sm[];
+  const BatchFitcTallBlockParams& tp = vp.t;
+  const BatchFitcParams& p = tp.b;
+  const BatchVaParams& va = vp.va;
+  const int n = p.n, m = p.m, d = p.d, t = threadIdx.x;
+  const int nth = 2 + p.n_ell;
+  const int64_t pb = blockIdx.x;
+  const Lds s = carve(sm, n, m, d);
+  const Ws w = carve_ws(tp.ws + pb * tp.ws_stride, n, m, s.ld, tp.nfold);
+  const double* x = p.x + pb * n * d;
+  const double* y = p.y + pb * n;
+  double* il = s.th + 20;
+  int info = p.info[pb];
+  int done = p.steps_done[pb];
+  double stale = p.stale[pb];
+  for (int e = t; e < m * d; e += FT) s.zs[e] = p.z[pb * m * d + e];
+  if (t < nth) s.th[t] = p.theta[pb * nth + t];
+  double obj[GPS_N_OBJ];
+  VaStats ys = {0.0, 0.0, 0.0};
+  if (info == 0 && va_launch_scores(p, va.va_every)) ys = va_target_stats(y, n);
+  const int64_t nva = va_rows(p.itr, va.va_every);
+  int vfrom = p.step0;  // the first step of this launch whose row is not written yet
+  const int ntrain = p.nsteps;
+  const int neval = ntrain + (p.do_final ? 1 : 0);
+  double sf2 = 0.0, sn2 = 0.0;
+  for (int st = 0; st < neval && info == 0; ++st) {
+    const bool fin = st == ntrain;
+    __syncthreads();  // θ and Z (loaded, or the previous step's update) are visible
+    const double lsn = s.th[nth - 1];
+    sf2 = exp(s.th[0]);
+    sn2 = exp(fin && p.stale_noise ? stale : lsn);
+    const double bq = t < d ? s.th[1 + (p.n_ell == 1 ? 0 : t)] : 0.0;
+    if (t < d) il[t] = exp(-bq);  // th + 20: beside θ, never over it
+    __syncthreads();
+    if (!fin) stale = lsn;
+    info = forward(s, w, x, y, n, m, d, tp.nfold, sf2, sn2, obj);
+    if (info || fin) break;
+    const int gi = p.step0 + st;
+    if (gi % va.va_every == 0) {  // workgroup-uniform
+      va_checkpoint(s, va, pb, gi / va.va_every, nva, m, d, sf2, sn2, ys);
+      vfrom = gi + 1;
+    }
+    double g[FG], gz[GPS_BATCH_MAX_D], value;
+    int col;
+    bool lane0;
+    info = block_gradient(s, w, x, y, n, m, d, p.objective, tp.nfold, sf2, value, nullptr, g, gz,
+                          &col, &lane0);
+    if (info) break;
+    const double gn = sn2 * g[1];
+    // every read of θ and Z of this step lies before block_gradient()'s closing barriers
+    if (t == 0) {
+      const int64_t si = pb * p.itr + p.step0 + st;
+      p.values[si] = value;
+      double nv = s.th[0] - p.lr * (g[0] + sf2 * g[1]);
+      s.th[0] = nv;
+      p.thetas[si * nth] = nv;
+      double tot = 0.0;
+#pragma unroll
+      for (int q = 0; q < GPS_BATCH_MAX_D; ++q)
+        if (q < d) {
+          if (p.n_ell != 1) {
+            nv = s.th[1 + q] - p.lr * g[2 + q];
+            s.th[1 + q] = nv;
+            p.thetas[si * nth + 1 + q] = nv;
+          }
+          tot += g[2 + q];
+        }
+      if (p.n_ell == 1) {
+        nv = s.th[1] - p.lr * tot;
+        s.th[1] = nv;
+        p.thetas[si * nth + 1] = nv;
+      }
+      nv = s.th[nth - 1] - p.lr * gn;
+      s.th[nth - 1] = nv;
+      p.thetas[si * nth + nth - 1] = nv;
+    }
+    if (lane0)
+#pragma unroll
+      for (int k = 0; k < GPS_BATCH_MAX_D; ++k)
+        if (k < d) s.zs[col * d + k] -= p.lr_z * gz[k];
+    ++done;
+  }
+  __syncthreads();
+  train_write_back<FT>(p, pb, t, s.th, s.zs, info, done, stale);
+  if (t == 0) p.info[pb] = info;
+  va_finish(s, p, va, pb, info, vfrom, sf2, sn2, obj, ys);
+}
+
 }  // namespace
 
 size_t batch_fitc_tall_block_lds_bytes(int n, int m, int d) {
@@ -839,6 +933,36 @@ hipError_t launch_batch_fitc_tall_block(const BatchFitcTallBlockParams& tp, hipS
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(batch_fitc_tall_block_kernel, dim3((unsigned)p.nprob), dim3(FT),
                      batch_fitc_tall_block_lds_bytes(p.n, p.m, p.d), s, tp);
+  return hipGetLastError();
+}
+
+int batch_fitc_tall_block_va_steps(int64_t n, int64_t nv, int64_t va_every) {
+  const int64_t plain = batch_fitc_tall_block_steps(n);
+  const int64_t k = kBatchFitcVaRowBudget / (nv < 1 ? 1 : nv) * (va_every < 1 ? 1 : va_every);
+  return (int)(k < 1 ? 1 : (k < plain ? k : plain));
+}
+
+hipError_t launch_batch_fitc_tall_block_va(const BatchFitcTallBlockVaParams& vp, hipStream_t s) {
+  const BatchFitcTallBlockParams& tp = vp.t;
+  const BatchFitcParams& p = tp.b;
+  const BatchVaParams& va = vp.va;
+  if (p.mode != BATCH_MODE_TRAIN || !va.xv || !va.yv || !va.va_sc || va.nv < 1 ||
+      va.va_every < 1 || p.n < 1 || p.n > GPS_BATCH_FITC_TALL_MAX_N || p.m < 1 ||
+      p.m > GPS_BATCH_FITC_MAX_M || p.d < 1 || p.d > GPS_BATCH_MAX_D || p.nprob < 1 ||
+      (p.n_ell != 1 && p.n_ell != p.d) || p.nsteps < 0 ||
+      p.nsteps > batch_fitc_tall_block_va_steps(p.n, va.nv, va.va_every) || p.step0 < 0 ||
+      (int64_t)p.step0 + p.nsteps > p.itr || tp.nfold < 2 ||
+      tp.nfold > GPS_BATCH_BLOCK_MAX_FOLDS || tp.nfold > p.n ||
+      (p.objective != GPS_BLOCK_DSS && p.objective != GPS_BLOCK_KC) || !tp.ws ||
+      tp.ws_stride < batch_fitc_tall_block_ws_doubles(p.n, p.m, tp.nfold))
+    return hipErrorInvalidValue;
+  const hipError_t e = raise_dynamic_lds(
+      (const void*)batch_fitc_tall_block_va_kernel,
+      batch_fitc_tall_block_lds_bytes(GPS_BATCH_FITC_TALL_MAX_N, GPS_BATCH_FITC_MAX_M,
+                                      GPS_BATCH_MAX_D));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(batch_fitc_tall_block_va_kernel, dim3((unsigned)p.nprob), dim3(FT),
+                     batch_fitc_tall_block_lds_bytes(p.n, p.m, p.d), s, vp);
   return hipGetLastError();
 }
 

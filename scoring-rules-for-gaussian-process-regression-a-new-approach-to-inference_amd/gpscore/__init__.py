@@ -14,7 +14,9 @@ Drop-in layers:
                           ``es_value_and_grad_tall`` on the block-LOO energy score,
                           ``train_tall_validated`` / ``blockloo_train_tall_validated`` the tall
                           full-GP fits with a validation set scored step by step,
-                          ``fitc_blockloo_*_tall`` the tall FITC problems on DSS / KC;
+                          ``fitc_blockloo_*_tall`` the tall FITC problems on DSS / KC,
+                          ``fitc_train_tall_validated`` / ``fitc_blockloo_train_tall_validated``
+                          the tall FITC fits with a validation set scored step by step;
   * ``gpscore.dist``    — one process per GPU, FITC row sharding;
   * ``gpscore._lib``    — the ctypes binding of libgpscore.so (include/gpscore.h).
 """
@@ -27,6 +29,8 @@ from .batch import (BatchTrainResult, FitcBatchTrainResult, blockloo_train_tall,
                     fitc_blockloo_value_and_grad_tall, fitc_train_batch,
                     fitc_train_tall, fitc_value_and_grad_batch, fitc_value_and_grad_tall,
                     train_batch, train_tall, value_and_grad_batch, value_and_grad_tall,
-                    ValidatedTrainResult, blockloo_train_tall_validated, train_tall_validated)
+                    ValidatedTrainResult, blockloo_train_tall_validated, train_tall_validated,
+                    FitcValidatedTrainResult, fitc_blockloo_train_tall_validated,
+                    fitc_train_tall_validated)
 
 __version__ = "0.1.0"

@@ -194,6 +194,15 @@ SIGNATURES = {
                                               _P, _c_int, _P, _c_int, _c_i64, _c_dbl, _c_dbl, _P, _P,
                                               _c_i64, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _PI,
                                               _PI]),
+    "gps_fitc_train_tall_va": (_c_int, [_c_vp, _c_int, _c_i64, _P, _P, _c_i64, _c_int, _P, _c_int, _P,
+                                        _c_int, _c_i64, _c_dbl, _c_dbl, _P, _P, _c_i64, _c_i64, _P,
+                                        _P, _c_i64, _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _PI, _PI]),
+    "gps_fitc_blockloo_train_tall_va": (_c_int, [_c_vp, _c_int, _c_int, _c_i64, _P, _P, _c_i64,
+                                                 _c_int, _P, _c_int, _P, _c_int, _c_i64, _c_dbl,
+                                                 _c_dbl, _P, _P, _c_i64, _c_i64, _P, _P, _c_i64,
+                                                 _c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _PI,
+                                                 _PI]),
     "gps_comm_unique_id": (_c_int, [_c_cp]),
     "gps_comm_init": (_c_int, [_c_vp, _c_int, _c_int, _c_cp]),
     "gps_comm_init_local": (_c_int, [_c_vp, _c_int, _c_int, ctypes.c_longlong]),

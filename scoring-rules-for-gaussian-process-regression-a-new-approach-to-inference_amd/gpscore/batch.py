@@ -1,7 +1,7 @@
 """Batches of small full GPs and small FITC GPs, one workgroup per problem in one launch
 (DESIGN §19, §20), and their siblings for taller problems (§22, §24; the block-LOO DSS / KC
 objectives §26 for the full GP, §27 for FITC; the block-LOO energy score §32; a validation set
-scored inside the tall full-GP fits §34).
+scored inside the tall full-GP fits §34 and the tall FITC fits §37).
 
     vals, grads, objs, info = gpscore.value_and_grad_batch(X, y, theta, "loo_crps")
     res = gpscore.train_batch(X, y, (1.0, 1.0, 1.0), "loo_crps", lr=1.0, itr=250, Xt=Xt, yt=yt)
@@ -14,6 +14,8 @@ scored inside the tall full-GP fits §34).
     res = gpscore.train_tall_validated(X, y, theta0, Xv, yv, "loo_crps", itr=400, select="crps")  # §34
     res = gpscore.fitc_blockloo_train_tall(X, y, Z0, theta0, "kc", nfold=4, lr=0.1, itr=3000,
                                            Xt=Xt, yt=yt)                                # n <= 2048
+    res = gpscore.fitc_train_tall_validated(X, y, Z0, theta0, Xv, yv, "loo_crps", itr=2000,
+                                            va_every=10, select="crps")                 # §37
 
 The replicate loops of "SIMPLE-DATA FULL-comapre.py" (TT = 100 data sets of n = 120, three SGD
 fits each: SD:192-231, 277-301, 372-396) and contour-plot.R's n = 20 problems are many tiny,
@@ -257,6 +259,10 @@ _FITC = _Path("gps_fitc_grad_batch","gps_fitc_train_batch", BATCH_MAX_N, fitc=Tr
 _FITC_TALL = _Path("gps_fitc_grad_tall", "gps_fitc_train_tall", BATCH_FITC_TALL_MAX_N, fitc=True)
 _FITC_BLOCK = _Path("gps_fitc_blockloo_grad_tall", "gps_fitc_blockloo_train_tall",
                     BATCH_FITC_TALL_MAX_N, fitc=True, rule="block")
+_FITC_TALL_VA = _Path("gps_fitc_grad_tall", "gps_fitc_train_tall_va", BATCH_FITC_TALL_MAX_N,
+                      fitc=True, va=True)
+_FITC_BLOCK_VA = _Path("gps_fitc_blockloo_grad_tall", "gps_fitc_blockloo_train_tall_va",
+                       BATCH_FITC_TALL_MAX_N, fitc=True, rule="block", va=True)
 
 
 def _front(path, X, y, Z, theta, objective, nfold, num_sim, beta, rbf):
@@ -325,6 +331,32 @@ class ValidatedTrainResult(BatchTrainResult):
     va_scores: dict = None
     best_step: np.ndarray | None = None
     theta_best: np.ndarray | None = None
+
+
+@dataclass
+class FitcValidatedTrainResult(ValidatedTrainResult):
+    """fitc_train_tall_validated's outputs: ValidatedTrainResult's fields, ``Z`` (B, m, d) the final
+    inducing inputs, and ``va_Z`` (B, nva, m, d) the inducing inputs each validation row was scored
+    at (the SGD steps move Z, so θ alone does not name a row's model; the last row is ``Z``) — filled
+    when ``select`` is given or ``keep_z`` is true, else None.  With ``select``, ``Z_best`` (B, m, d)
+    stands beside ``best_step`` / ``theta_best``: the Z of the selected row, NaN where best_step is
+    −1."""
+    Z: np.ndarray = None
+    va_Z: np.ndarray | None = None
+    Z_best: np.ndarray | None = None
+
+
+def select_best_z(best_step, va_steps, va_Z):
+    """The Z pick beside select_best: ``best_step`` (B,) → Z_best (B, m, d), row r of ``va_Z`` (B,
+    nva, m, d) where va_steps[r] == best_step (the final pass's row for best_step == itr, which holds
+    the returned Z), NaN where best_step is −1."""
+    B = va_Z.shape[0]
+    zb = np.full((B,) + va_Z.shape[2:], np.nan)
+    row = {int(st): r for r, st in enumerate(va_steps)}
+    for q in range(B):
+        if best_step[q] >= 0:
+            zb[q] = va_Z[q, row[int(best_step[q])]]
+    return zb
 
 
 def _va_every(va_every):
@@ -397,9 +429,10 @@ def select_best(va_row, va_steps, theta0, thetas, theta):
 
 def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, beta=None, lr=1.0,
            lr_z=None, itr=400, draws=None, draw_sets=None, rng=None, Xt=None, yt=None, rbf=False,
-           stale_noise=False, ctx=None, Xv=None, yv=None, va_every=1, select=None):
+           stale_noise=False, ctx=None, Xv=None, yv=None, va_every=1, select=None, keep_z=False):
     """A path's training call: BatchTrainResult, FitcBatchTrainResult on a FITC path, or
-    ValidatedTrainResult on a path with a validation set (path.va: Xv, yv, va_every, select)."""
+    ValidatedTrainResult on a path with a validation set (path.va: Xv, yv, va_every, select;
+    FitcValidatedTrainResult and keep_z where the path is FITC too)."""
     f = _front(path, X, y, Z0, theta0, objective, nfold, num_sim, beta, rbf)
     B, es = f.B, path.rule == "es"
     itr, lr = _steps(itr, lr)
@@ -420,6 +453,8 @@ def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, bet
         select = _select_metric(select)
         va_steps = va_steps_of(itr, va_every)
         va_sc = np.empty((B, len(va_steps), len(SCORE_NAMES)))
+        va_Z = np.empty((B, len(va_steps), f.m, f.d)) \
+            if path.fitc and (select is not None or keep_z) else None
     if es:
         draws = _es_draws(draws, B, sets, f.n, f.nfold, f.num_sim, rng)
     ctx = ctx or _lib.default_context()
@@ -436,7 +471,8 @@ def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, bet
              *((ptr(Xv), ptr(yv), nv, va_every) if path.va else ()), ptr(Xt), ptr(yt), nt,
              GPS_BATCH_STALE_NOISE if stale_noise else 0, *((ptr(draws), sets) if es else ()),
              ptr(theta), *((ptr(Z),) if path.fitc else ()), ptr(values), ptr(thetas), ptr(obj),
-             ptr(mu), ptr(var), ptr(sc), *((ptr(va_sc),) if path.va else ()), _iptr(info),
+             ptr(mu), ptr(var), ptr(sc), *((ptr(va_sc),) if path.va else ()),
+             *((ptr(va_Z),) if path.va and path.fitc else ()), _iptr(info),
              _iptr(steps))
     res = dict(theta=theta, series={"objective": values, "theta": thetas},
                objectives=_objectives(obj), mu=mu, var=var,
@@ -447,6 +483,11 @@ def _train(path, X, y, Z0, theta0, objective=None, nfold=None, num_sim=None, bet
         va_scores = {k: va_sc[:, :, q].copy() for q, k in enumerate(SCORE_NAMES)}
         best, th_best = (None, None) if select is None else select_best(
             va_scores["test_" + select], va_steps, f.th, thetas, theta)
+        if path.fitc:
+            return FitcValidatedTrainResult(
+                va_steps=va_steps, va_scores=va_scores, best_step=best, theta_best=th_best, Z=Z,
+                va_Z=va_Z, Z_best=None if select is None else select_best_z(best, va_steps, va_Z),
+                **res)
         return ValidatedTrainResult(va_steps=va_steps, va_scores=va_scores, best_step=best,
                                     theta_best=th_best, **res)
     return FitcBatchTrainResult(Z=Z, **res) if path.fitc else BatchTrainResult(**res)
@@ -624,3 +665,31 @@ def fitc_blockloo_train_tall(X, y, Z0, theta0, objective="dss", nfold=4, lr=1e-3
     fitc_train_tall: arguments, refusals and FitcBatchTrainResult."""
     return _train(_FITC_BLOCK, X, y, Z0, theta0, objective, nfold, lr=lr, lr_z=lr_z, itr=itr, Xt=Xt,
                   yt=yt, stale_noise=stale_noise, ctx=ctx)
+
+
+def fitc_train_tall_validated(X, y, Z0, theta0, Xv, yv, objective="loo_crps", lr=1.0, lr_z=None,
+                              itr=400, va_every=1, select=None, keep_z=False, Xt=None, yt=None,
+                              stale_noise=False, ctx=None):
+    """fitc_train_tall with a validation set scored inside the fit (one gps_fitc_train_tall_va call,
+    DESIGN §37): the per-iteration validation series "KIN40K-COMPARE-ALL-FITC-20" carries commented
+    out (K20:258-264, 469-476), from Lm⁻¹, Lb⁻¹ and c as each step's forward leaves them.  Validation
+    arguments, ``va_every`` and ``select`` as train_tall_validated; a row's model is θ AND Z before
+    its step, so ``select`` (or ``keep_z``) also brings back ``va_Z``, every row's inducing inputs,
+    and ``select`` adds ``Z_best``.  The fit is bitwise fitc_train_tall's.  Returns
+    FitcValidatedTrainResult."""
+    return _train(_FITC_TALL_VA, X, y, Z0, theta0, objective, lr=lr, lr_z=lr_z, itr=itr, Xt=Xt,
+                  yt=yt, stale_noise=stale_noise, ctx=ctx, Xv=Xv, yv=yv, va_every=va_every,
+                  select=select, keep_z=keep_z)
+
+
+def fitc_blockloo_train_tall_validated(X, y, Z0, theta0, Xv, yv, objective="dss", nfold=4, lr=1e-3,
+                                       lr_z=None, itr=3000, va_every=1, select=None, keep_z=False,
+                                       Xt=None, yt=None, stale_noise=False, ctx=None):
+    """fitc_blockloo_train_tall with a validation set scored inside the fit (one
+    gps_fitc_blockloo_train_tall_va call; the series K20:737-743 carries commented out,
+    its pointwise scores).  Validation arguments, ``select``, ``keep_z`` and
+    FitcValidatedTrainResult as fitc_train_tall_validated; the fit is bitwise
+    fitc_blockloo_train_tall's."""
+    return _train(_FITC_BLOCK_VA, X, y, Z0, theta0, objective, nfold, lr=lr, lr_z=lr_z, itr=itr,
+                  Xt=Xt, yt=yt, stale_noise=stale_noise, ctx=ctx, Xv=Xv, yv=yv, va_every=va_every,
+                  select=select, keep_z=keep_z)

@@ -329,7 +329,7 @@ def _run_batch(who, sheets, TT, methods, accepts, why, route, train, what, m=Non
     ctx=)``.  A failed replicate of a method whose objective is in ``zero_for`` gets zero metrics
     (run_method's rule); of any other raises NotPositiveDefinite "...: <what> after k steps".
     Returns {method: {metric: array(TT), "theta"[, "Z" with m][, "failed" with zero_for]}}.
-    ``post`` (run_full_validated_batch): ``train`` also gets Xv= / yv=, the replicates' validation
+    ``post`` (run_full_validated_batch, run_fitc_validated_batch): ``train`` also gets Xv= / yv=, the replicates' validation
     rows, and post(entry, res, method, X, y, Xt, yt) adds to a method's entry."""
     from .gp import es_draws
     for name, meth in methods.items():
@@ -563,3 +563,60 @@ def run_fitc_blockloo_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=No
             X, y, Z0, th0, meth.objective, nfold=nfold, lr_z=meth.lr_z, **kw),
         _FITC_INFO + ", (2 + f) m + k: of fold f's B)", m=m, zero_for=("kc",), itr=itr, seed=seed,
         reseed=reseed, stale_noise=stale_noise, ctx=ctx)
+
+
+def run_fitc_validated_batch(sheets, TT=10, methods=None, m=20, itr=None, seed=None, reseed=True,
+                             stale_noise=True, va_every=1, select=None, ctx=None, nfold=4):
+    """run_fitc_batch / run_fitc_blockloo_batch with every replicate's validation split (va_x /
+    va_y) scored inside the fits, step by step: the series K20 carries commented out
+    (K20:258-264, 469-476, 737-743).  Pointwise methods go through ONE fitc_train_tall_validated
+    call each, dss / kc through ONE fitc_blockloo_train_tall_validated call; ``methods`` defaults to
+    K20_METHODS' crps, nlml, logs, dss and kc entries.  A method whose objective is es raises
+    ValueError: FITC has no energy-score batch path.  Data replicates, θ0 and Z0 are drawn in run's
+    order, so with the same ``seed`` this fits the problems run_fitc_batch /
+    run_fitc_blockloo_batch fit, and the standard entries — {metric: array(TT), "Z", "theta"} and,
+    for dss / kc, "failed" — are theirs: a failed kc replicate gets zero metrics, a failed dss or
+    pointwise replicate raises NotPositiveDefinite.  Added per method: "va_scores" {name: array(TT,
+    nva)} over SCORE_NAMES, "va_steps" (nva,), and with ``select`` (a metric of
+    batch.SELECT_METRICS) "best_step" array(TT) and "selected" {metric: array(TT)}: the test metrics
+    at each replicate's (theta_best, Z_best), from one more fitc_train_tall(itr=0) call for the
+    replicates whose best row is not the final one; the others (and a replicate with no finite row)
+    keep the first call's metrics."""
+    from .batch import (_select_metric, _va_every, fitc_blockloo_train_tall_validated,
+                        fitc_train_tall_validated)
+    if methods is None:
+        methods = {k: K20_METHODS[k] for k in ("crps", "nlml", "logs", "dss", "kc")}
+    va_every, select = _va_every(va_every), _select_metric(select)
+
+    def train(X, y, th0, Z0, meth, **kw):
+        if meth.objective in BLOCK_BATCH_OBJS:
+            return fitc_blockloo_train_tall_validated(
+                X, y, Z0, th0, objective=meth.objective, nfold=nfold, lr_z=meth.lr_z,
+                va_every=va_every, select=select, **kw)
+        return fitc_train_tall_validated(X, y, Z0, th0, objective=meth.objective, lr_z=meth.lr_z,
+                                         va_every=va_every, select=select, **kw)
+
+    def post(entry, res, meth, X, y, Xt, yt):
+        if meth.objective not in BLOCK_BATCH_OBJS:
+            entry.pop("failed", None)  # run_fitc_batch's entries carry none
+        entry["va_scores"] = {k: v.copy() for k, v in res.va_scores.items()}
+        entry["va_steps"] = res.va_steps.copy()
+        if select is None:
+            return
+        entry["best_step"] = res.best_step.copy()
+        sel = {k: np.array(entry[k], dtype=np.float64) for k in METRICS}
+        redo = np.flatnonzero((res.best_step >= 0) & (res.best_step != res.va_steps[-1]))
+        if redo.size:
+            r2 = fitc_train_tall(X[redo], y[redo], res.Z_best[redo], res.theta_best[redo], itr=0,
+                                 Xt=Xt[redo], yt=yt[redo], ctx=ctx)
+            for k in METRICS:
+                sel[k][redo] = r2.scores["test_" + k]
+        entry["selected"] = sel
+
+    return _run_batch(
+        "run_fitc_validated_batch", sheets, TT, methods,
+        tuple(BATCH_OBJS) + tuple(BLOCK_BATCH_OBJS),
+        "which has no validated batch path (FITC has no energy-score batch path)",
+        lambda o: "run(kind=\"fitc\")", train,
+        _FITC_INFO + ", (2 + f) m + k: of fold f's B)", m=m, zero_for=("kc",), itr=itr, seed=seed,
+        reseed=reseed, stale_noise=stale_noise, ctx=ctx, post=post)
