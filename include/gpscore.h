@@ -181,6 +181,14 @@ enum {
                              products and of the predictive product) or never read (its columns
                              >= n*); 0: every block multiplied.  Same values bitwise for finite
                              operands. */
+  GPS_OPT_GEMM_PIPE = 32,   /* 1 (default): full 128-tiles of the store and column-reduction GEMM
+                             kernels run the pipelined steady-state loop (the LDS stores of the
+                             prefetched slice issued between the MFMAs of the last two k steps,
+                             fragment reads a fixed distance ahead, issue order pinned); 0: the
+                             loop of before.  Edge tiles, k-scaled launches, the row-norm
+                             epilogues, the 64-tile and small kernels and the stream-K tail's
+                             tiles run the loop of before either way.  Same values bitwise
+                             (DESIGN §38). */
 };
 int gps_ctx_set_option(gps_ctx* ctx, int key, int value);
 
@@ -285,6 +293,11 @@ int gps_gemm_diag(gps_ctx* ctx, const gps_gemm_desc* d, const double* A, const d
  * count, -1 on a refused description.  Needs no device. */
 int64_t gps_gemm_schedule(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int slots,
                           int32_t* plan, int32_t* items, int64_t cap);
+/* Diagnostics, beside gps_gemm_schedule: whether that launch's kernel would be told to run the
+ * pipelined loop of its full 128-tiles when GPS_OPT_GEMM_PIPE is `pipe` — 1, or 0 where launch_gemm
+ * clears the request (the option off, 64-tiles, the small kernel, the row-norm epilogues, a
+ * k-scaled launch); -1 on a refused description.  Needs no device. */
+int gps_gemm_pipe_resolved(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int pipe);
 
 /* Diagnostics: the factorisation with its fused inverse as gps_potrf runs it (the same upload,
  * buffers, options, graph capture and replay), everything it wrote copied back whole

@@ -197,6 +197,7 @@ int gemm(gps_ctx* ctx, int al, int bl, int epi, const GemmParams& p, hipStream_t
   GemmParams q = p;
   if (q.map_mode == 0) q.map_mode = ctx->fo.gemm_map;
   if (!ctx->fo.gemm_live) q.m_live = q.n_live = 0;  // GPS_OPT_GEMM_LIVE off: every block multiplied
+  q.pipe = ctx->fo.gemm_pipe;  // GPS_OPT_GEMM_PIPE (launch_gemm clears it where the loop is not compiled)
   // the stream's slabs: gemm_plan may split K on small grids; an explicit 64-tile split uses them
   if (epi == EPI_STORE && (q.ksplit == 1 || q.tile == 64) && !q.ws) {
     DBuf& ws = st == ctx->side      ? ctx->ws_side
@@ -895,6 +896,7 @@ int gps_ctx_set_option(gps_ctx* ctx, int key, int value) {
       ctx->fo.dag_kbatch = (value & 15) < 2 ? 0 : value;
       return 0;
     case GPS_OPT_GEMM_LIVE: ctx->fo.gemm_live = value != 0; return 0;
+    case GPS_OPT_GEMM_PIPE: ctx->fo.gemm_pipe = value != 0; return 0;
     case GPS_OPT_DAG_TILE_FORM:
       ARGCHK(value >= 0 && (value & 15) <= 8 && (value >> 8) == 0 && ((value & 15) || !value),
              "GPS_OPT_DAG_TILE_FORM must be 0 or minlen | d << 4 with minlen in 1..8 and d in 0..15");

@@ -910,4 +910,27 @@ int64_t gps_gemm_schedule(const gps_gemm_desc* d, const int32_t* kr, int have_ks
   return n;
 }
 
+int gps_gemm_pipe_resolved(const gps_gemm_desc* d, const int32_t* kr, int have_kscale, int pipe) {
+  if (!d) return fail(nullptr, -1, "gps_gemm_pipe_resolved: bad argument");
+  DiagExtents x;
+  std::string why;
+  if (!diag_check(*d, true, have_kscale != 0, true, kr, true, true, x, why))
+    return fail(nullptr, -1, "gps_gemm_pipe_resolved: " + why);
+  static double mark[2];  // (as gps_gemm_schedule: nothing is launched, no array is touched)
+  GemmParams p = desc_params(*d);
+  p.A = p.B = mark; p.C = p.out0 = p.out1 = mark; p.w = mark;
+  p.kscale = have_kscale ? mark : nullptr;
+  p.kr = d->tri == TRI_KR_J ? kr : nullptr;
+  if (own_slabs(*d) || (d->epi == EPI_STORE && (p.ksplit == 1 || p.tile == 64))) {
+    p.ws = mark;
+    p.ws_cap = kSplitWsDoubles;
+  }
+  p.pipe = pipe;  // (what gemm() copies from the context's option)
+  GemmLaunchInfo info{};
+  GemmParams q;
+  if (launch_gemm(d->lay_a, d->lay_b, d->epi, p, nullptr, &info, &q) != hipSuccess)
+    return fail(nullptr, -1, "gps_gemm_pipe_resolved: launch_gemm refuses the launch");
+  return q.pipe;
+}
+
 }  // extern "C"

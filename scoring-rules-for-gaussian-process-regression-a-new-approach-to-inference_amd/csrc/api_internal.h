@@ -131,6 +131,7 @@ struct FactorOpts {
   int overlap = 1;                     // GPS_OPT_OVERLAP
   int gemm_map = 0;                    // GPS_OPT_GEMM_MAP: tile-order override (A/B measurements)
   int gemm_live = 1;                   // GPS_OPT_GEMM_LIVE: the GEMMs' live-extent hints (gemm())
+  int gemm_pipe = 1;                   // GPS_OPT_GEMM_PIPE: the 128-tile GEMMs' pipelined loop (gemm())
   int dag = 1;                         // GPS_OPT_DAG: persistent factorisation of the bottom blocks
   int dag_tiles = 20;                  // GPS_OPT_DAG_TILES
   int dag_tiles_full = 40;             // GPS_OPT_DAG_TILES_FULL: the full GP's cap (0: dag_tiles)

@@ -94,6 +94,12 @@ struct GemmParams {
   int sk_alone;              // the launch runs without a concurrent forked product (potrf_inv_rec's
                              // trailing update when nothing is forked beside it): the stream-K
                              // tail fills its last round (GPS_OPT_STREAM_K = 2, the default)
+  int pipe;                  // 1: full 128-tiles of the store and column-reduction kernels run the
+                             // pipelined steady-state loop (LDS stores under the MFMAs, issue
+                             // order pinned: gemm_tile's mainloop_pipe; GPS_OPT_GEMM_PIPE, DESIGN
+                             // §38).  Set by gemm(); cleared by launch_gemm where that loop is not
+                             // compiled (64-tiles, the small kernel, the row-norm epilogues) or
+                             // not taken (k-scaled launches, priority off).  Same bits either way
   // Row norms behind a running persistent factorisation (EPI_ROWSQ, TRI_K_LE_J, tri_off 0, 128
   // tiles, no split): column tile j needs row tile j of L⁻¹ only.
   //   dep_mode 1 (the dependent launch): each workgroup takes the heaviest column tile whose row

@@ -334,6 +334,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
 
   // ---- global -> register staging (PER doubles of A and of B per thread) ----
   dv2 ra[NQ], rb[NQ];
+  // (load_plain below copies this lambda without the k-scale part, store_a / store_b copy
+  // store_tile's two halves: an edit of the index arithmetic here is mirrored there)
   auto load_tile = [&](int k0) {
     if constexpr (ALAY == LAY_T) {  // A stored [k][i]
       const int k = tid / TPR, i = (tid % TPR) * 2;
@@ -398,6 +400,64 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
       }
     }
   };
+  // The pipelined loop's staging (mainloop_pipe below): load_tile without the k-scale test, which
+  // its caller has made once per tile (the loop must stay one basic block), and store_tile in its
+  // two halves.  Copies, not a refactoring of the two lambdas above: the old loop's schedule is not
+  // pinned, and the kernels that keep it (the row norms) lost 3 % when its source form changed.
+  auto load_plain = [&](int k0) {
+    if constexpr (ALAY == LAY_T) {
+      const int k = tid / TPR, i = (tid % TPR) * 2;
+      const dv2* src = reinterpret_cast<const dv2*>(p.A + (int64_t)(k0 + k) * p.lda + row0 + i);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) ra[q] = src[q * TPR];
+    } else {
+      const int i = tid / TPI, k = (tid % TPI) * PER;
+      const dv2* src = reinterpret_cast<const dv2*>(p.A + (int64_t)(row0 + i) * p.lda + k0 + k);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) ra[q] = src[q];
+    }
+    if constexpr (BLAY == LAY_N) {
+      const int k = tid / TPR, j = (tid % TPR) * 2;
+      const dv2* src = reinterpret_cast<const dv2*>(p.B + (int64_t)(k0 + k) * p.ldb + col0 + j);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) rb[q] = src[q * TPR];
+    } else {
+      const int j = tid / TPI, k = (tid % TPI) * PER;
+      const dv2* src = reinterpret_cast<const dv2*>(p.B + (int64_t)(col0 + j) * p.ldb + k0 + k);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) rb[q] = src[q];
+    }
+  };
+  auto store_a = [&](int buf) {
+    double* As = smem + buf * STAGE;
+    if constexpr (ALAY == LAY_T) {
+      const int k = tid / TPR, i = (tid % TPR) * 2;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) *reinterpret_cast<dv2*>(&As[rowoff(k) + i + 2 * TPR * q]) = ra[q];
+    } else {
+      const int i = tid / TPI, k = (tid % TPI) * PER;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        As[rowoff(k + 2 * q) + i] = ra[q].x;
+        As[rowoff(k + 2 * q + 1) + i] = ra[q].y;
+      }
+    }
+  };
+  auto store_b = [&](int buf) {
+    double* Bs = smem + buf * STAGE + BK * LS;
+    if constexpr (BLAY == LAY_N) {
+      const int k = tid / TPR, j = (tid % TPR) * 2;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) *reinterpret_cast<dv2*>(&Bs[rowoff(k) + j + 2 * TPR * q]) = rb[q];
+    } else {
+      const int j = tid / TPI, k = (tid % TPI) * PER;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        Bs[rowoff(k + 2 * q) + j] = rb[q].x;
+        Bs[rowoff(k + 2 * q + 1) + j] = rb[q].y;
+      }
+    }
+  };
 
   d4 acc[MI][MI];
 #pragma unroll
@@ -437,6 +497,10 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
   // produces and check_info discards anyway (as §29 states for its clipped term).  Skipped
   // columns that are merely never read (n_live) differ where the full loop had non-zeros.
   constexpr bool LIVE = EDGE && (EPI == EPI_STORE || EPI == EPI_COLRED);
+  // The pipelined steady-state loop (mainloop_pipe below) is compiled where the edge copy is, at
+  // TILE = 128: not in the stream-K tail's tiles, the 64-tile kernels or the row-norm epilogues
+  // (launch_gemm clears GemmParams::pipe for those).
+  constexpr bool PIPE = LIVE && TILE == 128;
   const int mrem = LIVE && p.m_live > 0 ? p.m_live - row0 : TILE;  // live rows / columns of this tile
   const int nrem = LIVE && p.n_live > 0 ? p.n_live - col0 : TILE;
   const bool edge = mrem < TILE || nrem < TILE;
@@ -507,10 +571,110 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int ti, int tj, i
       mma((nk - 1) & 1);
       row_dot((nk - 1) & 1, kb + (nk - 1) * BK);
     };
-    // the edge copy: same staging, barriers and double buffer (a wave with nothing live still
-    // reaches every barrier), live blocks only in its compute
-    if (!edge) mainloop(compute);
-    else mainloop(compute_edge);
+    // The pipelined loop (GemmParams::pipe): the same loads, fragment reads, MFMAs and
+    // LDS stores as mainloop(compute), in an order the source pins.  The body is one basic block
+    // (no k-scale, priority raised, not an edge tile: decided once per tile below) cut into five
+    // scheduling regions by sched_barrier(0) — the top (first k step's fragments, the global
+    // loads of slice it+1) and the four k steps — and inside a k step the sched_group_barrier
+    // groups fix where, between that step's 16 MFMAs, the next step's fragment reads and the LDS
+    // stores of the prefetched slice are issued:
+    //   k step 0, 1: 4 × (fragment reads of the next step, 1 MFMA), 12 MFMAs
+    //   k step 2   : 4 × (fragment reads of step 3, 1 MFMA), 8 × (one A store, 1 MFMA), 4 MFMAs
+    //   k step 3   : 8 × (one B store, 1 MFMA), 8 MFMAs, then lgkmcnt(0) and the barrier
+    // The vmcnt wait for the prefetched slice thus stands in front of the first A store, 36 MFMAs
+    // after the loads were issued, and no longer behind the last MFMA.
+    // Hazard: the stores of iteration `it` go to buffer (it+1)&1.  Its last readers are the
+    // fragment reads of compute(it−1), which every wave issued and waited for (they feed its
+    // MFMAs) before it arrived at the barrier that ended iteration it−1 (for it = 0: the
+    // prologue's barrier, before which nothing reads the buffers); every wave storing here has
+    // passed that barrier.  This iteration's own fragment reads go to buffer it&1 only, and the
+    // barrier at its end orders the stores before compute(it+1)'s reads as in the parent's loop.
+    // Step 3's fragment reads are issued before the first store, in the source too: the compiler
+    // cannot tell the two buffers apart and keeps LDS reads and writes in source order.
+    // Bits: every accumulator sees the same MFMA chain (slices ascending, k steps ascending).
+    auto mainloop_pipe = [&]() {
+      constexpr int DSR = 0x100, DSW = 0x200, MFMA = 0x8;  // sched_group_barrier masks
+      auto frags = [&](const double* As, const double* Bs, int kk, double (&fa)[MI], double (&fb)[MI]) {
+        const int krow = rowoff(kk * 4 + (lane >> 4)) + (lane & 15);
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) fa[mi] = As[krow + wr * WT + mi * 16];
+#pragma unroll
+        for (int ni = 0; ni < MI; ++ni) fb[ni] = Bs[krow + wc * WT + ni * 16];
+      };
+      auto mmas = [&](const double (&fa)[MI], const double (&fb)[MI]) {
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < MI; ++ni)
+            acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
+      };
+      // One k step's region: the next step's fragment reads (if any) a pair per MFMA from the
+      // step's first MFMA on, then the eight LDS stores of one operand (if any) one per MFMA, then
+      // the step's other MFMAs.  (A fragment read is a ds_read2_b64 of two blocks or two
+      // ds_read_b64, a group of two takes either; a group that finds fewer instructions of its
+      // kind in the region — the k-major operands' four 16-byte stores, stores the compiler
+      // paired — is simply short.)
+      auto pin = [&](auto reads, auto stores) {
+        constexpr int R = decltype(reads)::value ? 4 : 0, W = decltype(stores)::value ? 8 : 0;
+#pragma unroll
+        for (int g = 0; g < R; ++g) {
+          __builtin_amdgcn_sched_group_barrier(DSR, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(MFMA, 1, 0);
+        }
+#pragma unroll
+        for (int g = 0; g < W; ++g) {
+          __builtin_amdgcn_sched_group_barrier(DSW, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(MFMA, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(MFMA, 16 - R - W, 0);
+      };
+      constexpr std::true_type yes{};
+      constexpr std::false_type no{};
+      for (int it = 0; it < nk - 1; ++it) {
+        const double* As = smem + (it & 1) * STAGE;
+        const double* Bs = As + BK * LS;
+        const int nb = (it + 1) & 1;
+        double a0[MI], b0[MI], a1[MI], b1[MI];
+        frags(As, Bs, 0, a0, b0);
+        __builtin_amdgcn_sched_barrier(0);
+        load_plain(kb + (it + 1) * BK);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+        frags(As, Bs, 1, a1, b1);  // ---- k step 0
+        mmas(a0, b0);
+        pin(yes, no);
+        __builtin_amdgcn_sched_barrier(0);
+        frags(As, Bs, 2, a0, b0);  // ---- k step 1
+        mmas(a1, b1);
+        pin(yes, no);
+        __builtin_amdgcn_sched_barrier(0);
+        frags(As, Bs, 3, a1, b1);  // ---- k step 2
+        store_a(nb);
+        mmas(a0, b0);
+        pin(yes, yes);
+        __builtin_amdgcn_sched_barrier(0);
+        store_b(nb);               // ---- k step 3
+        mmas(a1, b1);
+        pin(no, yes);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(0);
+        __syncthreads();
+      }
+      compute((nk - 1) & 1);
+    };
+    // Decided once per tile, uniformly for the workgroup, as `edge` is: the pipelined loop where
+    // it is compiled and asked for, else the edge copy (same staging, barriers and double buffer
+    // — a wave with nothing live still reaches every barrier — live blocks only in its compute)
+    // or the loop above.
+    bool piped = false;
+    if constexpr (PIPE) piped = p.pipe && !edge && !p.kscale && p.prio;
+    if (piped) {
+      if constexpr (PIPE) mainloop_pipe();
+    } else if (!edge) {
+      mainloop(compute);
+    } else {
+      mainloop(compute_edge);
+    }
   }
   if constexpr (EPI == EPI_ROWSQ_DOT) {
     if (rdot && tid < TILE) p.out1[row0 + tid] = dacc;
@@ -856,6 +1020,7 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
   if (tile == 16 || tile == 32) {  // small kernel: tile = block edge, ksplit = waves per block
     if (epi != EPI_STORE || p.kscale) return hipErrorInvalidValue;
     p.m_live = p.n_live = 0;
+    p.pipe = 0;
     const int wpt = plan.ksplit;
     if (wpt != 1 && wpt != 2 && wpt != 4) return hipErrorInvalidValue;
     const int64_t tt = small_tiles(p, tile);
@@ -918,6 +1083,7 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
       return hipErrorInvalidValue;
     q.map_mode = 0;
     q.prio = 0;
+    q.pipe = 0;
     q.slab_xcd = 0;
     q.sk_dp = q.sk_wgs = 0;
     if (resolved) return hipErrorInvalidValue;  // (its tiles are taken at run time: no schedule)
@@ -975,6 +1141,9 @@ hipError_t launch_gemm(int alay, int blay, int epi, const GemmParams& pin, hipSt
   // the FITC row-norm launches and the Λ-scaled SYRK ran 0.4 % slower with it), 2 = every launch
   // (GPS_OPT_GEMM_PRIO 0 and 2 measured slower and were removed in round 6: DESIGN §6.31)
   q.prio = (epi == EPI_STORE || epi == EPI_COLRED) && !q.kscale;
+  // the pipelined loop (gemm_tile's mainloop_pipe): compiled in the 128-tile store and
+  // column-reduction kernels, for launches without a k-scale at raised priority — the same set
+  q.pipe = q.pipe != 0 && tile == 128 && q.prio;
   // slice-major per XCD: split-K launches whose tile index is the plain (or remapped) raster
   q.slab_xcd = g_slab_xcd && q.ksplit > 1 && q.sk_wgs == 0 &&
                (q.map_mode == 0 || q.map_mode == 2) && (q.lower_out || q.tri == TRI_NONE);

@@ -36,6 +36,7 @@ GPS_OPT_DAG_TILES_FULL = 28
 GPS_OPT_DAG_KBATCH = 29
 GPS_OPT_DAG_TILE_FORM = 30
 GPS_OPT_GEMM_LIVE = 31  # 1 (default): edge tiles skip the MFMA blocks that lie in the padding
+GPS_OPT_GEMM_PIPE = 32  # 1 (default): full 128-tiles run the pipelined GEMM loop
 # the library's defaults of those two (api_internal.h): 40-tile blocks in the full GP's fit, and
 # batches of 8 K tiles in the blocks above GPS_OPT_DAG_TILES (bit 8 of the batch option)
 DAG_TILES_FULL_DEFAULT = 40
@@ -103,6 +104,7 @@ SIGNATURES = {
     "gps_gemm_diag_check": (_c_int, [ctypes.POINTER(GemmDesc), _c_int, _c_int, _c_int, _PI, _c_int,
                                      _c_int]),
     "gps_gemm_schedule": (_c_i64, [ctypes.POINTER(GemmDesc), _PI, _c_int, _c_int, _PI, _PI, _c_i64]),
+    "gps_gemm_pipe_resolved": (_c_int, [ctypes.POINTER(GemmDesc), _PI, _c_int, _c_int]),
     "gps_gemm_diag": (_c_int, [_c_vp, ctypes.POINTER(GemmDesc), _P, _P, _P, _P, _P, _PI, _P, _P,
                                _PI]),
     "gps_potrf_diag": (_c_int, [_c_vp, _c_i64, _P, _c_i64, _P, _P, _P, _PI, _PI]),

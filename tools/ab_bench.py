@@ -6,7 +6,8 @@
            graph (GPS_OPT_GRAPH), tiny (GPS_OPT_TINY_GEMM),
            pre (GPS_OPT_PRED_PRE), dag (GPS_OPT_DAG), dagt (GPS_OPT_DAG_TILES), dep (GPS_OPT_FITC_DEP),
            dagtf (GPS_OPT_DAG_TILES_FULL), kbatch (GPS_OPT_DAG_KBATCH: B | g << 4),
-           form (GPS_OPT_DAG_TILE_FORM: minlen | d << 4), live (GPS_OPT_GEMM_LIVE)
+           form (GPS_OPT_DAG_TILE_FORM: minlen | d << 4), live (GPS_OPT_GEMM_LIVE),
+           pipe (GPS_OPT_GEMM_PIPE)
 Variants are interleaved round-robin for --rounds rounds; prints the median ms/unit.
 """
 import argparse
@@ -28,7 +29,7 @@ KEYS = {"map": _lib.GPS_OPT_GEMM_MAP, "ov": _lib.GPS_OPT_OVERLAP,
         "graph": _lib.GPS_OPT_GRAPH, "tiny": _lib.GPS_OPT_TINY_GEMM, "pre": _lib.GPS_OPT_PRED_PRE,
         "dag": _lib.GPS_OPT_DAG, "dagt": _lib.GPS_OPT_DAG_TILES, "arch": _lib.GPS_OPT_AR_CHUNKS, "dagg": _lib.GPS_OPT_DAG_GROUP, "sk": _lib.GPS_OPT_STREAM_K, "dagwg": _lib.GPS_OPT_DAG_WGS, "order": _lib.GPS_OPT_DAG_ORDER, "sxcd": _lib.GPS_OPT_SLAB_XCD, "dep": _lib.GPS_OPT_FITC_DEP,
         "dagtf": _lib.GPS_OPT_DAG_TILES_FULL, "kbatch": _lib.GPS_OPT_DAG_KBATCH, "form": _lib.GPS_OPT_DAG_TILE_FORM,
-        "live": _lib.GPS_OPT_GEMM_LIVE}
+        "live": _lib.GPS_OPT_GEMM_LIVE, "pipe": _lib.GPS_OPT_GEMM_PIPE}
 
 
 def main():
@@ -76,7 +77,7 @@ def main():
     phs = {v: [] for v, _ in variants}
     defaults = {KEYS["dagwg"]: 0, KEYS["dagtf"]: _lib.DAG_TILES_FULL_DEFAULT,
                 KEYS["kbatch"]: _lib.DAG_KBATCH_DEFAULT, KEYS["form"]: _lib.DAG_TILE_FORM_DEFAULT,
-                KEYS["live"]: 1}  # options a variant sets and the next one might not (reset first)
+                KEYS["live"]: 1, KEYS["pipe"]: 1}  # options a variant sets and the next one might not (reset first)
     for _ in range(args.rounds):
         for name, opts in variants:
             for key, val in {**defaults, **opts}.items():
