@@ -66,7 +66,8 @@ enum {
  * gps_fitc_blockloo_grad_tall / gps_fitc_blockloo_train_tall, and the vector-layer
  * diagnostic gps_vec_diag, and the validated fits gps_full_train_tall_va /
  * gps_full_blockloo_train_tall_va and gps_fitc_train_tall_va /
- * gps_fitc_blockloo_train_tall_va.
+ * gps_fitc_blockloo_train_tall_va, and the block / energy-score / joint kernels'
+ * diagnostic gps_block_diag.
  * The binding refuses a mismatch at load. */
 #define GPS_ABI_VERSION 900
 int gps_version(void);
@@ -398,6 +399,62 @@ int gps_fitc_contract_diag(gps_ctx* ctx, int64_t nr, int64_t nc, int64_t nc_pad,
  * Entries of mu_loo / var_loo past n are never written and come back NaN. */
 int gps_vec_diag(gps_ctx* ctx, int which, const int64_t* dims, const double* scal,
                  const double* const* in, double* const* out);
+
+/* Diagnostics: the block-LOO, energy-score and joint-predictive kernels (csrc/kernels_block.hip,
+ * csrc/kernels_joint.hip, and fitc_grad_v / fitc_grad_y of csrc/kernels_fitc_grad.hip) one
+ * production launch_* call at a time on host arrays (tests/test_gpu_block.py).  As
+ * gps_vec_diag: the arguments are judged before anything touches the device (-1 with the reason in
+ * gps_last_error; the launchers' own refusals — odd cols / ld / m_pad, bp % 64 for es_dist, S < 2
+ * or Sp < S + 1 for es_reduce, joint_cov's bp % 128, d outside 1..GPS_MAX_D and ks < 1 — are among
+ * them), and on the device everything is NaN beforehand, with a 16-double NaN gap after every
+ * array.  dims: 8 integers, scal: 8 doubles, in: 12 pointer slots, out: 4.  An input is dense on
+ * the host ([rows][cols]) and has the row stride given in dims on the device.  An output is its
+ * device image: [rows][ld] doubles and the 16 of the gap after it, so what the kernel left alone
+ * (row gaps, the gap, entries it must not write) comes back NaN.  "in/out": the kernel reads the
+ * array too; its first contents are taken from the host image (the row gaps stay NaN whatever the
+ * host holds there).  An optional operand that is NULL here is NULL in the launch.
+ *   which  launcher            dims                          in -> out
+ *   0  launch_fold_grad        {b, ldp, ldh, ldg}; scal      {PI [b][b], H|NULL, r [b], w|NULL}
+ *                               {c0, c1, c2, c3, gr, gw}      -> {G [b][ldg], g [b]}
+ *   1  launch_row_dots         {rows, cols, lda, ldb, same}  {A, B|NULL, t|NULL [cols]} ->
+ *                               same 1: B is A's own array    {at|NULL, ab|NULL [rows]}
+ *   2  launch_lr_fold_vec      {mode, b, bp}                 {lam, x, at, ab, r, c, w, gc, q [b]}
+ *                                                             (those the mode reads) -> {o1, o2 [bp]}
+ *                                                             (o2 may be NULL in mode 1)
+ *   3  launch_lr_combine       {rows, rows_pad, cols, ldx,   {X, Y, lam, rs|NULL, u1|NULL, v1|NULL,
+ *                               ldy, ldo}; scal {c0, c1, c2}  u2|NULL, v2|NULL} -> {out [rows_pad][ldo]}
+ *   4  launch_fold_sum         {nslab, skip, len, stride,    {slab [nslab][len], base|NULL,
+ *                               inplace}; scal {sgn}          base2|NULL} -> {dst [len]}; inplace 1:
+ *                                                             dst is base (in/out); one NaN slab follows
+ *   5  launch_fold_logdet      {m, b}                        {ldf, ldb [m], lam [b]} -> {out [1]}
+ *   6  launch_row_scale        {rows, cols, ld}              {scale [rows]} -> {M in/out}
+ *   7  launch_vec_mul          {n}                           {a, b} -> {out [n]}
+ *   8  launch_blk_mdiag        {n, n_pad, m_pad, ldf, ldus,  {F, US, U [n][m_pad], gd, lam, v, alpha
+ *                               ldu, ldy, alias}              [n]} -> {md, sc [n_pad], Y [n_pad][ldy]};
+ *                                                             alias 1: Y is US (in/out, in[1] NULL)
+ *   9  launch_ns_init          {b, bp, ldc}; scal {scale,    {C [b][b]|NULL} -> {Y [bp][bp]}
+ *                               pad}
+ *   10 launch_diag_add_const   {n, ld}; scal {c}             {} -> {M [n][ld] in/out}
+ *   11 launch_sym_avg          {n, ld}                       {} -> {M [n][ld] in/out}
+ *   12 launch_scaled_row       {b, bp}; scal {scale}         {src [b]} -> {dst [bp]}
+ *   13 launch_row_axpy         {rows, cols, ldc, ldz}        {Z, sv [rows]} -> {C [rows][ldc] in/out}
+ *   14 launch_ns_resid         {n, ld}                       {T [n][n]} -> {out [1]}
+ *   15 launch_es_dist          {S, bp, ldd}                  {Z [S][bp], Zh [S+1][bp]} -> {D [ldd][ldd]}
+ *   16 launch_es_reduce        {S, Sp, ldd, grad}; scal      {} -> {D [Sp][ldd] in/out, rs|NULL,
+ *                               {beta}                        cs|NULL [Sp], out [1]}; D's rows >= S and
+ *                                                             columns > S are NaN going in
+ *   17 launch_joint_cov        {b, bp, d, ks, stride}; scal  {x [b][d], inv_ell [d], slab [ks][bp*bp]}
+ *                               {sf2, sn2}                    -> {out [bp][bp]}; the slabs are NaN in the
+ *                                                             strict-upper 32-tiles, rows and columns >= b
+ *   18 launch_joint_resid      {b, bp}                       {y, mu [b]} -> {r [bp]}
+ *   19 launch_joint_dss        {b}                           {logdiag, t [b]} -> {out [1]}
+ *   20 launch_sign_fill        {npos, n}                     {} -> {dst [n]}
+ *   21 launch_row_add          {rows, cols, ld}              {mu [cols]} -> {M [rows][ld] in/out}
+ *   22 launch_fitc_grad_v      {n}                           {ulam, z, lam|NULL} -> {v [n]}
+ *   23 launch_fitc_grad_y      {rows, cols, ld, alias}       {U, UP|NULL [rows][cols], s1, s2|NULL}
+ *                                                             -> {Y [rows][ld]}; alias 1: Y is UP (in/out) */
+int gps_block_diag(gps_ctx* ctx, int which, const int64_t* dims, const double* scal,
+                   const double* const* in, double* const* out);
 
 /* on: 0 off, 1 per-kernel-class tags, 2 GEMM tags also carry layout/shape/tri/split-K/lda */
 int gps_prof_enable(gps_ctx* ctx, int on);

@@ -675,8 +675,6 @@ hipError_t launch_fold_grad(const double* PI, int64_t ldp, const double* H, int6
                             const double* r, const double* w, int b, double c0, double c1,
                             double c2, double c3, double gr, double gw, double* G, int64_t ldg,
                             double* g, hipStream_t s);
-hipError_t launch_add_diag(double* P, int64_t ld, const double* vals, int nreal, int npad,
-                           hipStream_t s);
 hipError_t launch_row_scale(double* M, int64_t ld, int rows, int cols, const double* scale,
                             hipStream_t s);
 hipError_t launch_vec_mul(const double* a, const double* b, int n, double* out, hipStream_t s);

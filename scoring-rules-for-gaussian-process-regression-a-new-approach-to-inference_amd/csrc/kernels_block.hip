@@ -202,23 +202,6 @@ hipError_t launch_lr_combine(const double* X, int64_t ldx, const double* Y, int6
   return hipGetLastError();
 }
 
-// P[i][i] += vals[i] for i < nreal; P[i][i] = 1 for nreal <= i < npad (diag(P, I) embedding)
-__global__ __launch_bounds__(256) void add_diag_kernel(double* __restrict__ P, int64_t ld,
-                                                       const double* __restrict__ vals, int nreal,
-                                                       int npad) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= npad) return;
-  double* p = P + (int64_t)i * ld + i;
-  *p = i < nreal ? *p + vals[i] : 1.0;
-}
-
-hipError_t launch_add_diag(double* P, int64_t ld, const double* vals, int nreal, int npad,
-                           hipStream_t s) {
-  hipLaunchKernelGGL(add_diag_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, P, ld, vals, nreal,
-                     npad);
-  return hipGetLastError();
-}
-
 // FITC block-LOO covariance (round 5, api.hip fitc_fold_cov): dst[e] = base[e] (+ base2[e]) +
 // sgn·Σ_{g ≠ skip} slab_g[e], the slabs in ascending order (fixed: bitwise reproducible); e < len
 __global__ __launch_bounds__(256) void fold_sum_kernel(const double* __restrict__ slab, int64_t stride,

@@ -115,6 +115,7 @@ SIGNATURES = {
     "gps_fitc_contract_diag": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _P, _P, _P, _c_dbl,
                                         _c_int, _PP, _PI64, _P, _PP, _P, _PP, _PP, _P, _P]),
     "gps_vec_diag": (_c_int, [_c_vp, _c_int, _PI64, _P, _PP, _PP]),
+    "gps_block_diag": (_c_int, [_c_vp, _c_int, _PI64, _P, _PP, _PP]),
     "gps_prof_enable": (_c_int, [_c_vp, _c_int]),
     "gps_prof_collect": (_c_int, [_c_vp, _c_cp, _c_i64]),
     "gps_phase_enable": (_c_int, [_c_vp, _c_int]),
@@ -360,6 +361,18 @@ def vec_diag_raw(h, which, dims, scal, ins, outs):
     return load().gps_vec_diag(h, which, d.ctypes.data_as(_PI64), ptr(sc), pi, po)
 
 
+def block_diag_raw(h, which, dims, scal, ins, outs):
+    """gps_block_diag: dims up to 8 integers, scal up to 8 doubles, ins (up to 12) / outs (up to 4)
+    lists of float64 arrays or None (None for a list itself: a NULL argument)."""
+    d = np.zeros(8, np.int64)
+    d[:len(dims)] = dims
+    sc = np.zeros(8)
+    sc[:len(scal)] = scal
+    pi = None if ins is None else _ptr_array(ins, 12)
+    po = None if outs is None else _ptr_array(outs, 4)
+    return load().gps_block_diag(h, which, d.ctypes.data_as(_PI64), ptr(sc), pi, po)
+
+
 def grad_contract_diag_raw(h, n, d, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a, out):
     return load().gps_grad_contract_diag(h, n, d, ptr(X), ptr(inv_ell), sf2, ptr(Ainv), ptr(Mx), ld,
                                          ptr(alpha), ptr(v), ptr(a), ptr(out))
@@ -529,6 +542,11 @@ class Context:
         """One vector-layer launch on host arrays (gps_vec_diag; diagnostics): dims / scal / ins /
         outs in the header's order, None where an array is absent; outs are written in place."""
         self.check(vec_diag_raw(self.h, which, dims, scal, ins, outs), "gps_vec_diag")
+
+    def block_diag(self, which, dims, ins, outs, scal=()):
+        """One launch of a block-LOO / energy-score / joint kernel on host arrays (gps_block_diag;
+        diagnostics): dims / scal / ins / outs per `which` as tabulated in include/gpscore.h."""
+        self.check(block_diag_raw(self.h, which, dims, scal, ins, outs), "gps_block_diag")
 
     def grad_contract_diag(self, X, inv_ell, sf2, Ainv, Mx, ld, alpha, v, a):
         """launch_grad_contract on host arrays (gps_grad_contract_diag; diagnostics): the
